@@ -31,6 +31,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import torch
 
@@ -108,6 +109,41 @@ def synthetic_batch(B, N, L, T, vocab, seed, device, all_valid=False, with_lengt
     labels = labels.masked_fill(pos >= tl[:, None], -100)
     out = (ids.to(device), mask.to(device), labels.to(device))
     return out + (lens.to(torch.int32),) if with_lengths else out     # lens stays on the host (the collator's knowledge)
+
+
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this much in all
+DUMP_PARAM_SAMPLE = 4096         # updated fp32 weights: at most this many fixed, seeded positions per parameter
+
+
+def seeded_sample(t, n, key: str):
+    """t flattened, or, when it has more than n elements, n of them at positions (repeats allowed) drawn by a generator seeded
+    from `key`: the same positions on every run and every build, since they depend only on the key and the element count."""
+    flat = t.reshape(-1)
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator().manual_seed(zlib.crc32(key.encode()))
+    idx = torch.randint(flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def snapshot_outputs(model, loss, logits, gnorm):
+    """What one train step hands its caller, copied to the host as float32: the loss, the logits, the global gradient norm
+    clip_grad_norm_ returned, and the fp32 master weights the optimizer step left (a seeded sample of each parameter, in
+    named_parameters() order).  The logits are a seeded sample when the whole tensor would not fit the budget."""
+    params = torch.cat([seeded_sample(p.detach(), DUMP_PARAM_SAMPLE, name).float()
+                        for name, p in model.named_parameters()]).cpu()
+    budget = (DUMP_BYTES - 4096) // 4 - params.numel() - 2          # float32 elements left for the logits (4 kB: the .npy headers)
+    out = {"loss": loss.detach().float().cpu(), "grad_norm": gnorm.detach().float().cpu(),
+           "logits": (logits.detach() if logits.numel() <= budget else seeded_sample(logits.detach(), budget, "logits")).float().cpu(),
+           "params_sample": params}
+    return {k: v.numpy() for k, v in out.items()}
+
+
+def write_outputs(outdir, arrays):
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def workload_tag(args) -> str:
@@ -275,11 +311,15 @@ def main():
     ap.add_argument("--fp8", action="store_true", help="MX block-scaled fp8 (e4m3 + E8M0 scales) forward GEMMs for the encoder's QKV / FFN-in "
                     "projections and the cross-K/V projection (BASELINE config 5); roofline then describes that kernel against the fp8 peak")
     ap.add_argument("--breakdown", action="store_true", help="print the per-op HIP-event breakdown to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last timed step computed (loss, "
+                    "logits, gradient norm, a seeded sample of the updated fp32 weights) as DIR/<name>.npy, float32, <= 64 MB in all")
     args = ap.parse_args()
     if args.cpu_worker:
         return cpu_worker(args)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: become one (BEFORE anything here touches a GPU) instead of measuring one GPU under an N-GPU label
         raise SystemExit(self_launch(args, sys.argv[1:]))
@@ -339,9 +379,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(all_valid, warmup, steps):
+    def measure(all_valid, warmup, steps, capture=False):
         """warm-up, then EXACTLY `steps` timed steps between two fences; one more step afterwards carries the per-launch
-        HIP-event probe (its event records would perturb the step they sit in)."""
+        HIP-event probe (its event records would perturb the step they sit in).  capture: snapshot what the last timed step
+        returned (before the probe step changes the weights) into the result's "outputs"."""
         batches = [synthetic_batch(B, N, L, T, cfg.vocab_size, seed=rank * 7919 + i, device=device, all_valid=all_valid,
                                    with_lengths=True) for i in range(NB)]
 
@@ -349,13 +390,14 @@ def main():
             ids, mask, labels, lens = batches[i % NB]
             # the batch arrives as from the data loader: device tensors + the collator's host-side lengths; offsets and the
             # packed-row index of the unpadded encoder are rebuilt from them inside the step (no per-batch cache)
-            loss = model(input_ids=ids, attention_mask=mask, labels=labels, passage_lengths=lens)[0]
+            loss, logits = model(input_ids=ids, attention_mask=mask, labels=labels, passage_lengths=lens)
             loss.backward()
-            U.clip_grad_norm_(model, 1.0)
+            gnorm = U.clip_grad_norm_(model, 1.0)
             optimizer.step()
             scheduler.step()
             model.zero_grad()
             loss_acc.add_(loss.detach())
+            return loss, logits, gnorm
 
         host_ms = None
         for i in range(warmup):
@@ -373,10 +415,11 @@ def main():
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(steps):
-            step(warmup + i)
+            last = step(warmup + i)
             marks[i + 1].record()
         fence()
         elapsed = time.perf_counter() - t0
+        outputs = snapshot_outputs(model, *last) if capture else None
         per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
         ops.probe = []
         step(warmup + steps)
@@ -401,12 +444,14 @@ def main():
         bf16_gemm = {"launches_per_step": nb, "achieved_tflops": round(fb / (tb * 1e-3) / 1e12, 1) if tb > 0 else 0.0,
                      "ms_per_step": round(tb, 3)}
         mxq = probe.get("mx_quantize", (0, 0.0, 0.0))
-        return dict(bf16_gemm=bf16_gemm, mxq_ms=mxq[1], elapsed=elapsed, ms=elapsed / steps * 1e3, median_ms=per_step[len(per_step) // 2], host_ms=host_ms,
+        return dict(outputs=outputs, bf16_gemm=bf16_gemm, mxq_ms=mxq[1], elapsed=elapsed, ms=elapsed / steps * 1e3, median_ms=per_step[len(per_step) // 2], host_ms=host_ms,
                     probe=probe, fl_exec=fl_exec, fl_proj=fl_proj, xattn=xattn, valid_frac=float(lens_all.double().mean()) / L, n_l=n_l, t_ms=t_ms,
                     achieved=achieved, value=world * B * steps / elapsed,
                     step_frac=world * B / (elapsed / steps) * fl_exec / 1e12 / (PEAK_BF16_TFLOPS * world if args.fp8 else peak * world))
 
-    main_run = measure(args.all_valid, args.warmup, args.steps)
+    main_run = measure(args.all_valid, args.warmup, args.steps, capture=args.dump_outputs is not None and rank == 0)
+    if main_run["outputs"] is not None:
+        write_outputs(args.dump_outputs, main_run["outputs"])
     av_run = None
     if not args.all_valid and args.all_valid_steps > 0:
         av_run = measure(True, 3, args.all_valid_steps)

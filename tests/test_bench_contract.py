@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -48,6 +49,29 @@ def test_synthetic_batch_recipe():
     assert m2.all()
     i4, m4, l4, lens4 = bench.synthetic_batch(3, 5, 64, 8, 32128, seed=1, device="cpu", with_lengths=True)
     assert torch.equal(i4, ids) and torch.equal(m4, mask) and torch.equal(lens4.long(), mask.sum(-1)) and not lens4.is_cuda
+
+
+def test_dump_sample_is_fixed_and_fits_the_budget(tmp_path):
+    """--dump-outputs: the sampled positions depend only on the key and the size (two builds compare element for element),
+    small tensors go whole, and the files are float32 within 64 MB even when the logits must be sampled."""
+    t = torch.arange(100000, dtype=torch.float32)
+    a, b = bench.seeded_sample(t, 500, "w"), bench.seeded_sample(t.clone(), 500, "w")
+    assert a.shape == (500,) and torch.equal(a, b) and not torch.equal(a, bench.seeded_sample(t, 500, "v"))
+    assert torch.equal(bench.seeded_sample(t[:300], 500, "w"), t[:300])
+    model = torch.nn.Sequential(torch.nn.Linear(64, 3000), torch.nn.Linear(3000, 4))
+    big = torch.randn(4, 8, 600000)                                       # 77 MB of logits: more than the whole budget
+    arrays = bench.snapshot_outputs(model, torch.tensor(2.5), big, torch.tensor(0.75))
+    bench.write_outputs(str(tmp_path), arrays)
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["grad_norm.npy", "logits.npy", "loss.npy", "params_sample.npy"]
+    loaded = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(v.dtype == np.float32 for v in loaded.values())
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    assert loaded["loss"].shape == loaded["grad_norm"].shape == () and loaded["loss"] == 2.5 and loaded["grad_norm"] == 0.75
+    assert loaded["params_sample"].size == 4096 + 3000 + 4096 + 4
+    assert np.array_equal(loaded["params_sample"][4096:7096], model[0].bias.detach().numpy())
+    small = bench.snapshot_outputs(model, torch.tensor(1.0), big[:, :, :1000], torch.tensor(0.0))["logits"]
+    assert np.array_equal(small, big[:, :, :1000].numpy())                 # whole when it fits
 
 
 def _run_bench(argv, env_extra=None, timeout=120):
@@ -117,3 +141,24 @@ def test_bench_prints_one_json_line_last(tmp_path):
     assert out["median_step_ms"] > 0 and "traffic_source" in rf
     av = out["all_valid"]
     assert av["value"] > 0 and av["steps"] >= 1 and "no padding" in av["passage_lengths"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeat(tmp_path):
+    """--dump-outputs: the same arguments give the same inputs, so two runs write the same outputs of the last timed step (bit for bit
+    under LAKO_DETERMINISTIC=1), and --steps is the number of timed steps on the result line."""
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = _run_bench(["--model", "small", "--batch", "2", "--n-passages", "3", "--seq-len", "64", "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--all-valid-steps", "0", "--dump-outputs", str(d)], {"LAKO_DETERMINISTIC": "1"}, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        outs.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = outs
+    assert sorted(a) == ["grad_norm", "logits", "loss", "params_sample"]
+    assert a["logits"].shape == (2, 8, FiDConfig.named("small").vocab_size) and a["logits"].dtype == np.float32
+    for k in a:
+        assert np.isfinite(a[k]).all(), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)

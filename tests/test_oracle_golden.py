@@ -7,6 +7,12 @@ from oracle import fid_t5_oracle as O
 from tests.util_golden import group, load_case
 
 CASES = ["tiny_a", "tiny_fact", "mid_a", "tiny_eos"]
+# test_train_steps on tiny_eos (|grad| 35-88, lr 1e-2): the CPU's vector width changes the summation order of torch's fp32 kernels,
+# and AdamW carries that rounding from step to step.  Measured against the fixtures with torch's default, AVX2 and AVX-512 kernels:
+# |grad| off by at most 3.1e-6 relative at steps 1-2 and 1.2e-4 at step 3, weights after step 3 by at most 1.7e-4, the loss
+# by at most 6.2e-6 (inside the common 2e-5).  Bounds: (relative |grad| allowance per step, weight atol), about 2.5-3x those.
+# The other cases agree within the common bounds on every vector width.
+TRAIN_TOL = {"tiny_eos": ((1e-5, 1e-5, 3e-4), 5e-4)}
 
 
 def test_bucket_tables(golden_dir):
@@ -64,16 +70,17 @@ def test_train_steps(name):
     T = z["labels"].shape[1]
     lr, wd, clip, warm, total = z["train_hparams"].tolist()
     seed = {"tiny_a": 1, "tiny_fact": 2, "mid_a": 3, "tiny_eos": 5}[name]
+    gn_rel, w_atol = TRAIN_TOL.get(name, ((0.0, 0.0, 0.0), 2e-5))
     state = {}
     for k in range(3):
         bi, bm, bl = O.synthetic_batch(B, N, L, T, dims.vocab_size, seed=seed + 200 + k)
         loss, gn = O.train_step(w, dims, state, bi, bm, bl, k, lr, wd, clip, int(warm), int(total), training=False)
         assert abs(loss - z["train_losses"][k]) < 2e-5
-        assert abs(gn - z["train_gnorms"][k]) < 1e-4
+        assert abs(gn - z["train_gnorms"][k]) < 1e-4 + gn_rel[k] * abs(float(z["train_gnorms"][k]))
         if k in (0, 2):
             ref = group(z, f"w_step{k + 1}/")
             for n, v in w.items():
-                torch.testing.assert_close(v, ref[n], atol=2e-5, rtol=1e-4, msg=lambda m, n=n: f"{n}: {m}")
+                torch.testing.assert_close(v, ref[n], atol=w_atol, rtol=1e-4, msg=lambda m, n=n: f"{n}: {m}")
 
 
 @pytest.mark.parametrize("name", CASES)
