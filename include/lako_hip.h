@@ -108,11 +108,17 @@ enum {
   LAKO_EPI_RESID = 2,   /* v = resid + dropout(v)                         (HF5:400,141 residual)    */
   LAKO_EPI_AUXMASK = 4, /* v = aux > 0 ? v * aux_scale : 0                (ReLU+dropout backward)   */
   LAKO_EPI_ATOMIC = 8,  /* C (fp32) += v with float atomics instead of a store                     */
-  LAKO_EPI_NORM_A = 16  /* (round 4) A is the UN-normalised input of a T5LayerNorm (HF5:236-256): the operand is
+  LAKO_EPI_NORM_A = 16, /* (round 4) A is the UN-normalised input of a T5LayerNorm (HF5:236-256): the operand is
                            bf16(norm_w * (A * rstd)), rstd = rsqrt(mean(A^2) + norm_eps), formed in the kernel's fragments exactly
                            as lako_rmsnorm_fwd would write it; optional side outputs norm_out (the normalised rows) and norm_rstd.
                            Only where the M <= 256 kernel runs (bf16, K % 32 == 0, K <= 1024): LAKO_E_UNSUPPORTED otherwise,
                            nothing launched — the caller then runs lako_rmsnorm_fwd + a plain product.                       */
+  LAKO_EPI_GATED = 32,  /* T5 v1.1 gated-GELU forward, fused: B = [Wi0; Wi1] ([2f, d]), C = pre [M, 2f] = [a | b] (ldc = 2f) and aux =
+                           h [M, f] (ldaux = f) = lako_gated_gelu_fwd(pre, drop) in the same epilogue, from the bf16-rounded a, b it
+                           stores (bit-identical to the two launches).  drop applies to h only.  The only flag of the call; bf16,
+                           alpha = 1, f % 128 == 0, K % 128 == 0, K >= 256; LAKO_E_UNSUPPORTED otherwise, nothing launched.        */
+  LAKO_EPI_GATED_BWD = 64 /* its backward, fused: the product is dh [M, f] (N = f, never stored), aux = pre [M, 2f] (ldaux = 2f), C =
+                           dpre [M, 2f] (ldc = 2f) = lako_gated_gelu_bwd(bf16(dh), pre, drop).  Same conditions as LAKO_EPI_GATED. */
 };
 typedef struct {
   const void* A; /* [M, K] row-major, lda */
@@ -391,6 +397,15 @@ int lako_cast(const float* src, void* dst, int64_t n, int dtype, lako_stream_t s
 /* ---- small helpers ------------------------------------------------------------------------------ */
 /* y = dropout_scale_mask(x) (used for the backward of residual-branch dropout, HF5:400,141) */
 int lako_dropout_apply(const void* x, void* y, int64_t n, int dtype, lako_dropout_t drop, lako_stream_t stream);
+/* gated-GELU feed-forward activation of T5 v1.1 / Flan-T5 (HF T5DenseGatedActDense).  pre [M, 2f] = [a | b] (the product with the
+ * [Wi0; Wi1] block), all operands contiguous row-major, 16-byte aligned, f % 8 == 0.
+ *   fwd: h [M, f] = dropout(gelu_new(a) ⊙ b), gelu_new(x) = ½x(1 + tanh(√(2/π)(x + 0.044715x³))) in fp32; the dropout mask is
+ *        lako_keep4's at element index m·f + n (the index the ReLU FFN's epilogue uses)
+ *   bwd: dpre [M, 2f] = [dh·keep·scale·b·gelu_new'(a) | dh·keep·scale·gelu_new(a)]
+ * No allocation, no synchronisation: both may be captured into a graph. */
+int lako_gated_gelu_fwd(const void* pre, void* h, int64_t M, int f, int dtype, lako_dropout_t drop, lako_stream_t stream);
+int lako_gated_gelu_bwd(const void* dh, const void* pre, void* dpre, int64_t M, int f, int dtype, lako_dropout_t drop,
+                        lako_stream_t stream);
 /* _shift_right (HF5:618-637): dec[b][0] = 0; dec[b][t] = labels[b][t-1] (−100 → 0) */
 int lako_shift_right(const int64_t* labels, int64_t* dec_ids, int B, int T, lako_stream_t stream);
 /* unpadded encoder input (round 4): the token ids of the valid positions of ids [BN, L], packed in (passage, position) order —

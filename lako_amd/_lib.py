@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("LAKO_LIB") or os.path.join(_HERE, "liblako_hip.so")  
 
 ABI_VERSION = 4          # include/lako_hip.h LAKO_ABI_VERSION this binding was written for
 LAKO_F32, LAKO_BF16, LAKO_FP8_E4M3 = 0, 1, 2
-EPI_RELU, EPI_RESID, EPI_AUXMASK, EPI_ATOMIC, EPI_NORM_A = 1, 2, 4, 8, 16
+EPI_RELU, EPI_RESID, EPI_AUXMASK, EPI_ATOMIC, EPI_NORM_A, EPI_GATED, EPI_GATED_BWD = 1, 2, 4, 8, 16, 32, 64
 
 i64, i32, u32, f32, vp = C.c_int64, C.c_int, C.c_uint32, C.c_float, C.c_void_p
 
@@ -124,6 +124,8 @@ SIGNATURES = {
     "lako_transpose_cast_batched": [vp, i32, vp, vp, vp, i32, i32, i32, vp],
     "lako_cast": [vp, vp, i64, i32, vp],
     "lako_dropout_apply": [vp, vp, i64, i32, Dropout, vp],
+    "lako_gated_gelu_fwd": [vp, vp, i64, i32, i32, Dropout, vp],
+    "lako_gated_gelu_bwd": [vp, vp, vp, i64, i32, i32, Dropout, vp],
     "lako_shift_right": [vp, vp, i32, i32, vp],
     "lako_pack_ids": [vp, vp, vp, i32, i32, vp],
     "lako_greedy_step": [vp, i64, i32, vp, i64, i32, vp, vp, vp, i64, i64, vp],

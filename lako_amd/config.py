@@ -26,6 +26,10 @@ class FiDConfig:
     # the table does not exist and the bias is zero.  False: the table of a checkpoint is ignored (the semantics of every current
     # transformers and of the golden fixtures); True: the table is a parameter and the bias is applied (engine.py "legacy").
     legacy_cross_bias: bool = False
+    # T5 v1.1 / Flan-T5: "gated-gelu" = HF T5DenseGatedActDense (gelu_new(x·Wi0ᵀ) ⊙ (x·Wi1ᵀ)), "relu" = v1.0 T5DenseActDense
+    feed_forward_proj: str = "relu"
+    # False: the checkpoint's own lm_head (logits = dec_out · lm_headᵀ, no d_model^-0.5 rescale); True: the head is `shared`, rescaled
+    tie_word_embeddings: bool = True
 
     @property
     def inner_dim(self) -> int:
@@ -33,12 +37,17 @@ class FiDConfig:
 
     @staticmethod
     def named(size: str, **over) -> "FiDConfig":
-        """t5-small / t5-base / t5-large dimensions (the `--model_size` flag, src/options.py:57)."""
+        """t5-small / t5-base / t5-large dimensions (the `--model_size` flag, src/options.py:57), and the T5 v1.1 / Flan-T5 sizes
+        (gated-GELU feed-forward, untied LM head)."""
+        v11 = dict(feed_forward_proj="gated-gelu", tie_word_embeddings=False)
         table = {
             "tiny": dict(vocab_size=64, d_model=32, d_kv=32, d_ff=64, num_layers=2, num_decoder_layers=2, num_heads=2),
             "small": dict(),
             "base": dict(d_model=768, d_ff=3072, num_layers=12, num_decoder_layers=12, num_heads=12),
             "large": dict(d_model=1024, d_ff=4096, num_layers=24, num_decoder_layers=24, num_heads=16),
+            "v1_1-small": dict(d_model=512, d_ff=1024, num_layers=8, num_decoder_layers=8, num_heads=6, **v11),
+            "v1_1-base": dict(d_model=768, d_ff=2048, num_layers=12, num_decoder_layers=12, num_heads=12, **v11),
+            "v1_1-large": dict(d_model=1024, d_ff=2816, num_layers=24, num_decoder_layers=24, num_heads=16, **v11),
         }
         if size not in table:
             raise ValueError(f"unknown model size {size!r}")
@@ -50,9 +59,10 @@ class FiDConfig:
     def from_hf(cfg) -> "FiDConfig":
         """Accept an HF `T5Config`-like object or a dict (duck-typed on the fields we use)."""
         get = (lambda k, d=None: cfg.get(k, d)) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
-        ff = get("feed_forward_proj", "relu")
-        if ff not in (None, "relu"):
-            raise ValueError(f"only the T5 v1.0 ReLU feed-forward is supported, got {ff!r}")
+        ff = get("feed_forward_proj", "relu") or "relu"
+        if ff not in ("relu", "gated-gelu"):
+            raise ValueError(f"only the T5 v1.0 ReLU and the T5 v1.1 gated-GELU feed-forward are supported, got {ff!r}")
+        tie = get("tie_word_embeddings", True)
         return FiDConfig(
             vocab_size=get("vocab_size"), d_model=get("d_model"), d_kv=get("d_kv"), d_ff=get("d_ff"),
             num_layers=get("num_layers"), num_decoder_layers=get("num_decoder_layers") or get("num_layers"),
@@ -61,12 +71,16 @@ class FiDConfig:
             dropout_rate=get("dropout_rate", 0.1), layer_norm_epsilon=get("layer_norm_epsilon", 1e-6),
             decoder_start_token_id=get("decoder_start_token_id", 0) or 0, pad_token_id=get("pad_token_id", 0) or 0,
             eos_token_id=get("eos_token_id", 1) if get("eos_token_id", 1) is not None else 1,
-            legacy_cross_bias=bool(get("legacy_cross_bias", False)))
+            legacy_cross_bias=bool(get("legacy_cross_bias", False)), feed_forward_proj=ff,
+            tie_word_embeddings=True if tie is None else bool(tie))
+
+    @property
+    def gated(self) -> bool:
+        return self.feed_forward_proj == "gated-gelu"
 
     def to_dict(self) -> dict:
         d = asdict(self)
-        d.update(model_type="t5", architectures=["FiDT5"], feed_forward_proj="relu", is_encoder_decoder=True,
-                 tie_word_embeddings=True)
+        d.update(model_type="t5", architectures=["FiDT5"], is_encoder_decoder=True)
         return d
 
     def to_json(self) -> str:

@@ -181,6 +181,58 @@ __host__ __device__ __forceinline__ bool lako_keep(uint32_t key, uint64_t idx, u
   lako_keep4(key, idx >> 2, thresh, k);
   return k[idx & 3];
 }
+// T5 v1.1 gelu_new(x) = ½x(1 + tanh(u)), u = √(2/π)(x + 0.044715x³), and its derivative, in fp32; tanh(u) = 1 − 2 / (1 + e^{2u})
+// (saturates to ±1 without a NaN).  ONE definition for the standalone kernels (rowops.hip) and the fused GEMM epilogues (gemm_nt4.h):
+// the same expressions, so the same roundings — the fused forms are bit-identical to the standalone ones.
+// Every multiply feeding an add is an explicit fmaf: with contraction left to the compiler it fused them differently inside the GEMM epilogue
+// than in the standalone kernel (1-ulp differences in da) — written out, both contexts compute the same operations.
+__device__ __forceinline__ void lako_gelu_new(float x, float& g, float& dg) {
+  const float k0 = 0.7978845608028654f, k1 = 0.044715f;
+  const float x2 = x * x;
+  const float u = k0 * __builtin_fmaf(k1 * x2, x, x);
+  const float r = __builtin_amdgcn_rcpf(1.f + __expf(2.f * u));
+  const float t = __builtin_fmaf(-2.f, r, 1.f);
+  const float s1 = 1.f + t;
+  g = 0.5f * x * s1;
+  const float q = __builtin_fmaf(-t, t, 1.f);
+  dg = __builtin_fmaf(0.5f, s1, 0.5f * x * q * k0 * __builtin_fmaf(3.f * k1, x2, 1.f));
+}
+// the element math of the gated activation on 8 consecutive h columns (bf16-rounded a, b and dh as floats; keep of each element)
+__device__ __forceinline__ void lako_gated_fwd8(const float (&a)[8], const float (&b)[8], const bool (&kp)[8], float scale, float (&h)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float g, dg;
+    lako_gelu_new(a[i], g, dg);
+    h[i] = kp[i] ? g * b[i] * scale : 0.f;
+  }
+}
+__device__ __forceinline__ void lako_gated_bwd8(const float (&a)[8], const float (&b)[8], const float (&gy)[8], const bool (&kp)[8], float scale,
+                                                float (&da)[8], float (&db)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float g, dg;
+    lako_gelu_new(a[i], g, dg);
+    const float y = kp[i] ? gy[i] * scale : 0.f;
+    da[i] = y * b[i] * dg;
+    db[i] = y * g;
+  }
+}
+// keep decisions of 8 consecutive elements from element idx0 (a multiple of 4); thresh 0 = dropout off: all kept
+__device__ __forceinline__ void lako_keep8(uint32_t key, uint64_t idx0, uint32_t thresh, bool (&k)[8]) {
+  if (!thresh) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) k[i] = true;
+    return;
+  }
+  bool x[4], y[4];
+  lako_keep4(key, idx0 >> 2, thresh, x);
+  lako_keep4(key, (idx0 >> 2) + 1, thresh, y);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    k[i] = x[i];
+    k[4 + i] = y[i];
+  }
+}
 static inline uint32_t lako_drop_thresh(float p) {   // 0 = dropout off
   double t = (double)p * 65536.0 + 0.5;
   if (t < 1) t = 1;

@@ -2279,6 +2279,38 @@ void launch_nt4(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
   }
 }
 
+// the fused gated-GELU epilogues (LAKO_EPI_GATED / _BWD, gemm_nt4.h EPI 3 / 4) on the 256-row four-wave tile.  The caller (lako_gemm_nt)
+// has checked gated_nt4_ok.
+bool gated_nt4_ok(const lako_gemm_nt_t* p) {
+  const bool fwd = p->flags == LAKO_EPI_GATED;
+  if (!fwd && p->flags != LAKO_EPI_GATED_BWD) return false;
+  const int64_t f = fwd ? p->N / 2 : p->N;
+  return p->in_dtype == LAKO_BF16 && p->out_dtype == LAKO_BF16 && p->alpha == 1.0f && p->aux != nullptr && f > 0 && f % 128 == 0 &&
+         (!fwd || p->N == 2 * f) && p->K % 128 == 0 && p->K >= 256 && p->lda % 8 == 0 && p->ldb % 8 == 0 && p->ldc == 2 * f &&
+         p->ldaux == (fwd ? f : 2 * f) && reinterpret_cast<uintptr_t>(p->C) % 16 == 0 && reinterpret_cast<uintptr_t>(p->aux) % 16 == 0 &&
+         reinterpret_cast<uintptr_t>(p->A) % 16 == 0 && reinterpret_cast<uintptr_t>(p->B) % 16 == 0 &&
+         (int64_t)256 * p->lda * 2 < (1ll << 31) && (fwd ? 2 * f : 256) * p->ldb * 2 < (1ll << 31) && (int64_t)256 * 2 * f * 2 < (1ll << 31);
+}
+void launch_nt4_gated(NtArgs a, hipStream_t s) {
+  a.tiles_m = cdiv(a.M, 256);
+  a.tiles_n = cdiv(a.N, 256);
+  a.group_m = a.tiles_n >= 8 ? 4 : 0;
+  a.dephase = 0;
+  a.debug = 0;
+  a.queue = nullptr;
+  a.epi_direct = 0;
+  a.row0 = 0;
+  int grid = a.tiles_m * a.tiles_n;
+  if (grid > 256) grid = 256;
+  if (a.flags == LAKO_EPI_GATED) {
+    LAKO_SET_MAX_LDS((&gemm_nt4_kernel<8, false, 3>), nt4::LDS_BYTES);
+    hipLaunchKernelGGL((gemm_nt4_kernel<8, false, 3>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);
+  } else {
+    LAKO_SET_MAX_LDS((&gemm_nt4_kernel<8, false, 4>), nt4::LDS_BYTES);
+    hipLaunchKernelGGL((gemm_nt4_kernel<8, false, 4>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);
+  }
+}
+
 template <typename T, typename TO>
 int launch_nt(const NtArgs& a_in, const lako_tuning_t& tu, hipStream_t s) {
   NtArgs a = a_in;
@@ -2498,6 +2530,12 @@ extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
     LAKO_CHECK_ARG(p->aux != nullptr && p->ldaux % 4 == 0, "lako_gemm_nt: AUXMASK needs aux, ldaux %% 4 == 0");
   }
   if (p->flags & LAKO_EPI_ATOMIC) LAKO_CHECK_ARG(p->out_dtype == LAKO_F32, "lako_gemm_nt: ATOMIC needs fp32 C");
+  if ((p->flags & (LAKO_EPI_GATED | LAKO_EPI_GATED_BWD)) && !gated_nt4_ok(p)) {
+    lako_set_error("lako_gemm_nt: the fused gated-GELU epilogues need bf16, alpha 1, no other flag, f %% 128 == 0, K %% 128 == 0, K >= 256, "
+                   "ldc = 2f, ldaux = f (forward) / 2f (backward), 16-byte aligned operands (M=%lld N=%lld K=%lld)", (long long)p->M,
+                   (long long)p->N, (long long)p->K);
+    return LAKO_E_UNSUPPORTED;
+  }
   LAKO_CHECK_ARG(p->drop.p >= 0.f && p->drop.p < 1.f, "lako_gemm_nt: dropout p out of range");
   NtArgs a{};
   a.row0 = 0;
@@ -2537,6 +2575,11 @@ extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
   }
   hipStream_t s = (hipStream_t)stream;
   const lako_tuning_t& tu = p->tuning ? *p->tuning : process_tuning();
+  if (p->flags & (LAKO_EPI_GATED | LAKO_EPI_GATED_BWD)) {
+    launch_nt4_gated(a, s);
+    LAKO_LAUNCH_CHECK();
+    return LAKO_OK;
+  }
   int rc = 0;
   if (p->in_dtype == LAKO_BF16) {
     if (p->out_dtype == LAKO_BF16) rc = launch_nt<bf16_t, bf16_t>(a, tu, s);

@@ -220,7 +220,122 @@ __device__ __forceinline__ void piece_offsets(uint32_t (&voff)[NP], int rows_val
   }
 }
 
+// the B pieces of a GATED tile (LAKO_EPI_GATED): tile column c of the tile at n0 is row c of the remapped operand — quarter q = c / 64
+// reads Wi0 (q even) or Wi1 (q odd, f rows further) at row n0 / 2 + 64·(q / 2) + c mod 64 (offsets relative to B + n0 / 2 rows), so that
+// each wave's 128 accumulator columns hold 64 gate columns and the 64 linear columns of the same h columns.  f % 128 == 0: every row valid.
+__device__ __forceinline__ void piece_offsets_gated(uint32_t (&voff)[8], int f, int64_t ld_bytes, int wave, int lane) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = (wave + 4 * j) * 8 + (lane >> 3);
+    const int c = (lane & 7) ^ ((row >> 1) & 7);
+    const int src = ((row >> 6) & 1) * f + (row >> 7) * 64 + (row & 63);
+    voff[j] = (uint32_t)(src * ld_bytes + c * 16);
+  }
+}
+
 }  // namespace nt4
+
+// ---- fused epilogues of the gated-GELU feed-forward (EPI 3: LAKO_EPI_GATED, EPI 4: LAKO_EPI_GATED_BWD).  The wave's region goes through its
+// LDS scratch as in nt4_epilogue below: a lane gets 8 consecutive columns (cj) of a row (rq + 4 it) of each 16-row pass, rounds them to bf16
+// and applies common.h's element math to exactly the values the standalone kernels would read back from HBM: bit-identical results.
+//  EPI 3: wave columns 0 … 63 are a, 64 … 127 are b of the h columns hc0 + 0 … 63 (piece_offsets_gated).  Every lane stores its 8 pre values at
+//         their [a | b] place; lanes cj < 8 take the b values of lane cj + 8 (same row) by a lane exchange and store 8 h values.
+//  EPI 4: the product is dh (never stored); the lane reads a and b of its 8 columns from pre (side loads issued before the pass's LDS reads)
+//         and stores da, db.
+template <int MT, int EPI>
+__device__ __forceinline__ void nt4_epilogue_gated(const NtArgs& a, f32x4 (&acc)[8][MT], char* smem, int wave, int wr, int wc, int m0, int n0) {
+  using namespace nt4;
+  const int le = fresh_lane();
+  const int r16e = le & 15, ge = le >> 4, cj = le & 15, rq = le >> 4;
+  char* ep = smem + SCRATCH + wave * 8192;
+  const int mw = m0 + wr * (MT * 16);
+  const int rows_v = min(MT * 16, a.M - mw);
+  constexpr bool FWD = EPI == 3;
+  const int f = FWD ? a.N / 2 : a.N;
+  const int hc0 = FWD ? n0 / 2 + wc * 64 : n0 + wc * 128;            // EPI 3: first h column of the wave; EPI 4: first dh column
+  const bool live = rows_v > 0 && (FWD || hc0 < f);
+  const int ldc_b = (int)a.ldc * 2, lda_b = (int)a.ldaux * 2;
+  // C (pre / dpre: [M, 2f]) and aux (h [M, f] / pre [M, 2f]) from the wave's first row; ranges end at the last valid row's last column
+  const auto crs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<bf16_t*>(a.C) + (int64_t)mw * a.ldc, 0,
+                                                     live ? (rows_v - 1) * ldc_b + 2 * f * 2 : 0, 0x00020000);
+  const auto xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(reinterpret_cast<const bf16_t*>(a.aux)) + (int64_t)mw * a.ldaux, 0,
+                                                     live ? (rows_v - 1) * lda_b + (FWD ? f : 2 * f) * 2 : 0, 0x00020000);
+  const int col = FWD ? (cj < 8 ? hc0 + cj * 8 : f + hc0 + (cj - 8) * 8) : hc0 + cj * 8;      // this lane's first column in C
+  const int hcol = FWD ? hc0 + (cj & 7) * 8 : col;                                            // … its first h / dh column
+  const int cvo = rq * ldc_b + col * 2;
+  const int hvo = (FWD && cj >= 8) ? (int)0x80000000 : rq * lda_b + hcol * 2;                 // EPI 3: h store; EPI 4: the a load
+  const uint32_t wr_base = (uint32_t)(r16e * 512), rd_base = (uint32_t)(rq * 512);
+  auto write_pass = [&](int mt) {
+#pragma unroll
+    for (int nt = 0; nt < 8; ++nt) *reinterpret_cast<f32x4*>(ep + wr_base + (((nt * 4 + ge) ^ r16e) * 16)) = acc[nt][mt];
+  };
+  write_pass(0);
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    u32x4 sa[4], sb[4];
+    if constexpr (!FWD) {
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        sa[it] = __builtin_amdgcn_raw_buffer_load_b128(xrs, hvo, (mt * 16 + it * 4) * lda_b, 0);
+        sb[it] = __builtin_amdgcn_raw_buffer_load_b128(xrs, hvo + f * 2, (mt * 16 + it * 4) * lda_b, 0);
+      }
+    }
+    f32x4 v[4][2];
+#pragma unroll
+    for (int it = 0; it < 4; ++it)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) v[it][h] = *reinterpret_cast<const f32x4*>(ep + rd_base + it * 2048 + (((2 * cj + h) ^ (it * 4 + rq)) * 16));
+    if (mt + 1 < MT) write_pass(mt + 1);      // (LDS executes the wave's accesses in order: the reads above see this pass)
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      bf16x8 o;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[4 * h + r] = (bf16_t)v[it][h][r];
+      const int row_l = mt * 16 + it * 4 + rq;
+      bool kp[8];
+      lako_keep8(a.drop_key, (uint64_t)(a.row0 + mw + row_l) * (uint64_t)f + (uint64_t)hcol, a.drop_thresh, kp);
+      if constexpr (FWD) {
+        const u32x4 ow = __builtin_bit_cast(u32x4, o);
+        __builtin_amdgcn_raw_buffer_store_b128(ow, crs, cvo, (mt * 16 + it * 4) * ldc_b, 0);
+        u32x4 bw;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bw[q] = (uint32_t)__shfl_xor((int)ow[q], 8, 64);
+        const bf16x8 bb = __builtin_bit_cast(bf16x8, bw);
+        float fa[8], fb[8], hh[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          fa[i] = (float)o[i];
+          fb[i] = (float)bb[i];
+        }
+        lako_gated_fwd8(fa, fb, kp, a.drop_scale, hh);
+        bf16x8 ho;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ho[i] = (bf16_t)hh[i];
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ho), xrs, hvo, (mt * 16 + it * 4) * lda_b, 0);
+      } else {
+        const bf16x8 ba = __builtin_bit_cast(bf16x8, sa[it]), bb = __builtin_bit_cast(bf16x8, sb[it]);
+        float fa[8], fb[8], gy[8], da[8], db[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          fa[i] = (float)ba[i];
+          fb[i] = (float)bb[i];
+          gy[i] = (float)o[i];
+        }
+        lako_gated_bwd8(fa, fb, gy, kp, a.drop_scale, da, db);
+        bf16x8 oa, ob;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          oa[i] = (bf16_t)da[i];
+          ob[i] = (bf16_t)db[i];
+        }
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, oa), crs, cvo, (mt * 16 + it * 4) * ldc_b, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ob), crs, cvo + f * 2, (mt * 16 + it * 4) * ldc_b, 0);
+      }
+    }
+  }
+}
 
 // ---- epilogue of one tile (shared by the bf16 kernels and the MX kernel below: the accumulator layout is the same).
 // The MFMA pipes idle while it runs (the accumulators are the next tile's too), so it is built for latency: the
@@ -235,6 +350,10 @@ __device__ __forceinline__ void piece_offsets(uint32_t (&voff)[NP], int rows_val
 template <int MT, bool SIDE, int EPI>
 __device__ __forceinline__ void nt4_epilogue(const NtArgs& a, f32x4 (&acc)[8][MT], char* smem, int wave, int wr, int wc, int m0, int n0) {
   using namespace nt4;
+  if constexpr (EPI == 3 || EPI == 4) {
+    nt4_epilogue_gated<MT, EPI>(a, acc, smem, wave, wr, wc, m0, n0);
+    return;
+  }
   const int le = fresh_lane();
   const int r16e = le & 15, ge = le >> 4, cj = le & 15, rq = le >> 4;
   char* ep = smem + SCRATCH + wave * 8192;
@@ -463,10 +582,13 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(NtArgs a) {
   }
   uint32_t voffA[MT], voffB[8];
   piece_offsets<MT>(voffA, min(BM, a.M - m0), lda_b, wave, lane);
-  piece_offsets<8>(voffB, min(BN, a.N - n0), ldb_b, wave, lane);
+  constexpr bool GATED = EPI == 3;      // (B rows remapped: piece_offsets_gated, base n0 / 2 rows)
+  auto b_rows = [&](int n) { return GATED ? (int64_t)(n / 2) : (int64_t)n; };
+  if constexpr (GATED) piece_offsets_gated(voffB, a.N / 2, ldb_b, wave, lane);
+  else piece_offsets<8>(voffB, min(BN, a.N - n0), ldb_b, wave, lane);
   // prologue: K-slices 0 and 1 of the first tile, then the k-half-0 fragments of step 0
   {
-    const uint64_t pA = reinterpret_cast<uint64_t>(a.A + (int64_t)m0 * lda_b), pB = reinterpret_cast<uint64_t>(a.B + (int64_t)n0 * ldb_b);
+    const uint64_t pA = reinterpret_cast<uint64_t>(a.A + (int64_t)m0 * lda_b), pB = reinterpret_cast<uint64_t>(a.B + b_rows(n0) * ldb_b);
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
 #pragma unroll
@@ -484,7 +606,7 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(NtArgs a) {
     tile_coords(has_next ? next_tile : tile, a.tiles_m, a.tiles_n, a.group_m, tm_, tn_);
     const int nm0 = tm_ * BM, nn0 = tn_ * BN;
     const char* Abase = a.A + (int64_t)m0 * lda_b;
-    const char* Bbase = a.B + (int64_t)n0 * ldb_b;
+    const char* Bbase = a.B + b_rows(n0) * ldb_b;
 
     f32x4 acc[8][MT];      // [n-tile][m-tile]; element r of lane (l & 15, g): C[m = mt·16 + (l & 15)][n = nt·16 + 4g + r]
     // the k-half-0 fragments of the tile's first K-step (buffer 0: landed and published by the previous tile's last counted wait + barrier
@@ -500,9 +622,10 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(NtArgs a) {
     // own first slices again (the pieces are always issued: the counted wait depends on it) — they land in buffers nobody reads any more
     auto next_tile_stream = [&]() {
       pA = reinterpret_cast<uint64_t>(a.A + (int64_t)nm0 * lda_b);
-      pB = reinterpret_cast<uint64_t>(a.B + (int64_t)nn0 * ldb_b);
+      pB = reinterpret_cast<uint64_t>(a.B + b_rows(nn0) * ldb_b);
       piece_offsets<MT>(voffA, min(BM, a.M - nm0), lda_b, wave, fresh_lane());
-      piece_offsets<8>(voffB, min(BN, a.N - nn0), ldb_b, wave, fresh_lane());
+      if constexpr (GATED) piece_offsets_gated(voffB, a.N / 2, ldb_b, wave, fresh_lane());
+      else piece_offsets<8>(voffB, min(BN, a.N - nn0), ldb_b, wave, fresh_lane());
     };
     if (NT_DBG(a, 64) && blockIdx.x == 0 && (threadIdx.x & 63) == 0 && kst < 128)      // (stamps) 4: the 100-MHz clock at the same point as 1
       reinterpret_cast<unsigned long long*>(a.queue)[((threadIdx.x >> 6) * 128 + kst) * 8 + 4] = __builtin_amdgcn_s_memrealtime();

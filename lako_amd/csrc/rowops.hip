@@ -495,6 +495,46 @@ __global__ __launch_bounds__(256) void dropout_apply_kernel(const T* __restrict_
   }
 }
 
+// ---- gated-GELU feed-forward activation (T5 v1.1, HF T5DenseGatedActDense) ---------------------------
+// pre [M, 2f] = [a | b] (the x·[Wi0; Wi1]ᵀ product), h [M, f] = dropout(gelu_new(a) ⊙ b), dropout index m·f + n — the index the ReLU
+// FFN's GEMM epilogue uses for the same site.  The element math is common.h's (lako_gated_fwd8 / _bwd8), shared with the fused
+// epilogues of gemm_nt4.h.  Each lane owns 8 consecutive h columns of one row (f % 8 == 0): one 16-byte load of a, one of b (bf16;
+// two each for fp32), one 16-byte store.
+template <typename T>
+__global__ __launch_bounds__(256) void gated_gelu_fwd_kernel(const T* __restrict__ pre, T* __restrict__ h, uint32_t n_chunks,
+                                                             uint32_t f8, DropDev dr) {
+  const int64_t f = (int64_t)f8 * 8;
+  for (uint32_t q = blockIdx.x * 256 + threadIdx.x; q < n_chunks; q += gridDim.x * 256) {
+    const uint32_t m = q / f8, c = (q - m * f8) * 8;
+    float a[8], b[8], o[8];
+    load8(pre + m * 2 * f + c, a);
+    load8(pre + m * 2 * f + f + c, b);
+    bool kp[8];
+    lako_keep8(dr.key, (uint64_t)m * f + c, dr.thresh, kp);
+    lako_gated_fwd8(a, b, kp, dr.scale, o);
+    store8(h + m * f + c, o);
+  }
+}
+
+// dpre [M, 2f] = [da | db]:  with γ = dh·keep·scale,  da = γ·b·gelu_new'(a),  db = γ·gelu_new(a)
+template <typename T>
+__global__ __launch_bounds__(256) void gated_gelu_bwd_kernel(const T* __restrict__ dh, const T* __restrict__ pre, T* __restrict__ dpre,
+                                                             uint32_t n_chunks, uint32_t f8, DropDev dr) {
+  const int64_t f = (int64_t)f8 * 8;
+  for (uint32_t q = blockIdx.x * 256 + threadIdx.x; q < n_chunks; q += gridDim.x * 256) {
+    const uint32_t m = q / f8, c = (q - m * f8) * 8;
+    float a[8], b[8], gy[8], da[8], db[8];
+    load8(pre + m * 2 * f + c, a);
+    load8(pre + m * 2 * f + f + c, b);
+    load8(dh + m * f + c, gy);
+    bool kp[8];
+    lako_keep8(dr.key, (uint64_t)m * f + c, dr.thresh, kp);
+    lako_gated_bwd8(a, b, gy, kp, dr.scale, da, db);
+    store8(dpre + m * 2 * f + c, da);
+    store8(dpre + m * 2 * f + f + c, db);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src, T* __restrict__ dst, int64_t n) {
   int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
@@ -1152,6 +1192,40 @@ extern "C" int lako_dropout_apply(const void* x, void* y, int64_t n, int dtype, 
   DropDev dr = make_drop(drop);
   DISPATCH_T(dtype, hipLaunchKernelGGL((dropout_apply_kernel<T>), dim3(elems_grid(n, 8)), dim3(256), 0,
                                        (hipStream_t)stream, (const T*)x, (T*)y, n, dr));
+  LAKO_LAUNCH_CHECK();
+  return LAKO_OK;
+}
+
+static int gated_args(const char* fn, const void* x, const void* pre, const void* y, int64_t M, int f, int dtype) {
+  LAKO_CHECK_ARG(dtype == LAKO_F32 || dtype == LAKO_BF16, "%s: bad dtype %d", fn, dtype);
+  LAKO_CHECK_ARG(M > 0 && f > 0 && f % 8 == 0, "%s: need M > 0 and d_ff a positive multiple of 8 (M=%lld, f=%d)", fn, (long long)M, f);
+  LAKO_CHECK_ARG(M * (int64_t)f / 8 < ((int64_t)1 << 31), "%s: M * f too large", fn);
+  LAKO_CHECK_ARG(x && pre && y, "%s: NULL operand", fn);
+  LAKO_CHECK_ALIGN(x, 16);
+  LAKO_CHECK_ALIGN(pre, 16);
+  LAKO_CHECK_ALIGN(y, 16);
+  return LAKO_OK;
+}
+
+extern "C" int lako_gated_gelu_fwd(const void* pre, void* h, int64_t M, int f, int dtype, lako_dropout_t drop, lako_stream_t stream) {
+  int rc = gated_args("lako_gated_gelu_fwd", h, pre, h, M, f, dtype);
+  if (rc != LAKO_OK) return rc;
+  const int64_t n = M * (int64_t)f / 8;
+  DropDev dr = make_drop(drop);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((gated_gelu_fwd_kernel<T>), dim3(elems_grid(n, 1)), dim3(256), 0, (hipStream_t)stream,
+                                       (const T*)pre, (T*)h, (uint32_t)n, (uint32_t)(f / 8), dr));
+  LAKO_LAUNCH_CHECK();
+  return LAKO_OK;
+}
+
+extern "C" int lako_gated_gelu_bwd(const void* dh, const void* pre, void* dpre, int64_t M, int f, int dtype, lako_dropout_t drop,
+                                   lako_stream_t stream) {
+  int rc = gated_args("lako_gated_gelu_bwd", dh, pre, dpre, M, f, dtype);
+  if (rc != LAKO_OK) return rc;
+  const int64_t n = M * (int64_t)f / 8;
+  DropDev dr = make_drop(drop);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((gated_gelu_bwd_kernel<T>), dim3(elems_grid(n, 1)), dim3(256), 0, (hipStream_t)stream,
+                                       (const T*)dh, (const T*)pre, (T*)dpre, (uint32_t)n, (uint32_t)(f / 8), dr));
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }

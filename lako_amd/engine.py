@@ -74,6 +74,14 @@ def build_layout(cfg: FiDConfig) -> list[Block]:
         blocks.append(Block(name, tuple(shape), members, transpose))
 
     Ld, Le = cfg.num_decoder_layers, cfg.num_layers
+
+    def wi(p):      # the FFN input projection: [f, d] (v1.0), or the gated form's two matrices as ONE [2f, d] block (rows [0, f) gate)
+        if cfg.gated:
+            return (2 * f, d), [(p + "DenseReluDense.wi_0.weight", 0, f), (p + "DenseReluDense.wi_1.weight", f, f)]
+        return (f, d), [(p + "DenseReluDense.wi.weight", 0, f)]
+
+    if not cfg.tie_word_embeddings:     # its gradient is the first one backward completes
+        add("lm_head", (cfg.vocab_size, d), [("lm_head.weight", 0, cfg.vocab_size)], True)
     add("dec.final_ln", (d,), [("decoder.final_layer_norm.weight", 0, d)])
     for i in range(Ld):
         p = f"decoder.block.{i}.layer."
@@ -84,7 +92,7 @@ def build_layout(cfg: FiDConfig) -> list[Block]:
         add(f"dec.{i}.cq", (inner, d), [(p + "1.EncDecAttention.q.weight", 0, inner)], True)
         add(f"dec.{i}.co", (d, inner), [(p + "1.EncDecAttention.o.weight", 0, d)], True)
         add(f"dec.{i}.ln2", (d,), [(p + "1.layer_norm.weight", 0, d)])
-        add(f"dec.{i}.wi", (f, d), [(p + "2.DenseReluDense.wi.weight", 0, f)], True)
+        add(f"dec.{i}.wi", *wi(p + "2."), True)
         add(f"dec.{i}.wo", (d, f), [(p + "2.DenseReluDense.wo.weight", 0, d)], True)
         add(f"dec.{i}.ln3", (d,), [(p + "2.layer_norm.weight", 0, d)])
     add("dec.rel", (nb, H), [("decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", 0, nb)])
@@ -102,7 +110,7 @@ def build_layout(cfg: FiDConfig) -> list[Block]:
                                              for j, n in enumerate("qkv")], True)
         add(f"enc.{i}.o", (d, inner), [(p + "0.SelfAttention.o.weight", 0, d)], True)
         add(f"enc.{i}.ln1", (d,), [(p + "0.layer_norm.weight", 0, d)])
-        add(f"enc.{i}.wi", (f, d), [(p + "1.DenseReluDense.wi.weight", 0, f)], True)
+        add(f"enc.{i}.wi", *wi(p + "1."), True)
         add(f"enc.{i}.wo", (d, f), [(p + "1.DenseReluDense.wo.weight", 0, d)], True)
         add(f"enc.{i}.ln2", (d,), [(p + "1.layer_norm.weight", 0, d)])
     add("enc.rel", (nb, H), [("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", 0, nb)])
@@ -216,6 +224,8 @@ class Engine:
         self.fp8 = bool(int(os.environ.get("LAKO_FP8", "0"))) if fp8 is None else bool(fp8)
         if self.fp8 and (dtype != torch.bfloat16 or not hasattr(ops, "gemm_nt_mx")):
             raise ValueError("fp8 GEMMs need the bf16 engine on the HIP op set")
+        if self.fp8 and cfg.gated:
+            raise ValueError("fp8 GEMMs (LAKO_FP8=1) are not implemented for the gated-GELU feed-forward (T5 v1.1 / Flan-T5)")
         self._w8: dict = {}      # block name → (e4m3 bytes [N, K], scales) of the weight shadow
 
     # ------------------------------------------------------------------------------------------
@@ -242,6 +252,9 @@ class Engine:
     def _bind(self):
         cfg = self.cfg
         self.shared = self._mat("shared")
+        # the LM head: `shared` × d_model^-0.5 (tied, v1.0), or its own matrix with alpha 1 (untied, v1.1)
+        self.lm_head = self.shared if cfg.tie_word_embeddings else self._mat("lm_head")
+        self.head_alpha = cfg.d_model ** -0.5 if cfg.tie_word_embeddings else 1.0
         self.kv_all = self._mat("dec.kv_all")
         self.enc_final, self.dec_final = self._vec("enc.final_ln"), self._vec("dec.final_ln")
         self.enc_rel, self.dec_rel = self._vec("enc.rel"), self._vec("dec.rel")
@@ -343,6 +356,15 @@ class Engine:
         self.ops.mx_quantize(x, xq, xs)
         self.ops.gemm_nt_mx(xq, xs, w8[0], w8[1], out, **epi)
 
+    def _fuse_gated(self, x, w, f):
+        """the encoder's gated-GELU products where the library's fused epilogues take the shape: "four" (LAKO_FUSE_GATED=0, the default):
+        the four-wave product + the standalone kernel, or "fused" (=1): both in the product's epilogue — bit-identical, measured slower
+        (0.895 against 0.721 ms per encoder layer at v1_1-base).  None (the decoder's skinny products, other shapes, the CPU
+        test double): the library's plain product + the standalone kernel."""
+        if not hasattr(self.ops, "gemm_nt_gated") or not self.ops.gated_fused_ok(x, w, f):
+            return None
+        return "fused" if os.environ.get("LAKO_FUSE_GATED", "0") == "1" else "four"
+
     def zero_grad(self):
         self.ops.zero_(self.G)
         self._g_fresh = True
@@ -443,8 +465,23 @@ class Engine:
         ops.gemm_nt(ctx, lw["o"].w, h1, resid=h, drop=dr(_enc_site(i, 1)))
         xn2 = self._buf(ws, f"e.xn2.{j}", (Me, d))
         a1 = self._buf(ws, f"e.a1.{j}", (Me, f))
-        self._norm_gemm_w(ws, h1, lw["ln2"].p, xn2, self._buf(ws, f"e.rs2.{j}", (Me,), torch.float32), eps, f"enc.{i}.wi", lw["wi"].w, a1, relu=True,
-                          drop=dr(_enc_site(i, 2)))
+        if cfg.gated:      # pre = [a | b] (kept for backward), a1 = dropout(gelu_new(a) ⊙ b)
+            pre = self._buf(ws, f"e.pre.{j}", (Me, 2 * f))
+            rs2 = self._buf(ws, f"e.rs2.{j}", (Me,), torch.float32)
+            fz = self._fuse_gated(xn2, lw["wi"].w, f)
+            if fz:      # both outputs from the product's epilogue (fused), or the same product + the standalone kernel (bit-identical)
+                ops.rmsnorm_fwd(h1, lw["ln2"].p, xn2, rs2, eps)
+                if fz == "fused":
+                    ops.gemm_nt_gated(xn2, lw["wi"].w, pre, a1, dr(_enc_site(i, 2)))
+                else:
+                    ops.gemm_nt_four(xn2, lw["wi"].w, pre)
+                    ops.gated_gelu_fwd(pre, a1, dr(_enc_site(i, 2)))
+            else:
+                self._norm_gemm_w(ws, h1, lw["ln2"].p, xn2, rs2, eps, f"enc.{i}.wi", lw["wi"].w, pre)
+                ops.gated_gelu_fwd(pre, a1, dr(_enc_site(i, 2)))
+        else:
+            self._norm_gemm_w(ws, h1, lw["ln2"].p, xn2, self._buf(ws, f"e.rs2.{j}", (Me,), torch.float32), eps, f"enc.{i}.wi", lw["wi"].w, a1,
+                              relu=True, drop=dr(_enc_site(i, 2)))
         if h_out is not None:
             ops.gemm_nt(a1, lw["wo"].w, h_out, resid=h1, drop=dr(_enc_site(i, 3)))
 
@@ -868,11 +905,15 @@ class Engine:
         ops.gemm_nt(c2, lw["co"].w, h2, resid=h1, drop=dr(_dec_site(i, 3)))
         xn3 = R(f"d.xn3.{i}", d)
         a1 = R(f"d.a1.{i}", f)
+        # gated: the product writes pre = [a | b] (kept for backward), then a1 = dropout(gelu_new(a) ⊙ b)
+        out1, act = (R(f"d.pre.{i}", 2 * f), {}) if cfg.gated else (a1, dict(relu=True, drop=dr(_dec_site(i, 4))))
         if fuse_norm:
-            ops.gemm_nt(h2, lw["wi"].w, a1, relu=True, drop=dr(_dec_site(i, 4)), norm=(lw["ln3"].p, eps, xn3, R(f"d.rs3.{i}", 0, torch.float32)))
+            ops.gemm_nt(h2, lw["wi"].w, out1, norm=(lw["ln3"].p, eps, xn3, R(f"d.rs3.{i}", 0, torch.float32)), **act)
         else:
             ops.rmsnorm_fwd(h2, lw["ln3"].p, xn3, R(f"d.rs3.{i}", 0, torch.float32), eps)
-            ops.gemm_nt(xn3, lw["wi"].w, a1, relu=True, drop=dr(_dec_site(i, 4)))
+            ops.gemm_nt(xn3, lw["wi"].w, out1, **act)
+        if cfg.gated:
+            ops.gated_gelu_fwd(out1, a1, dr(_dec_site(i, 4)))
         h_out = ws[f"d.h{i + 1}"][ch["r0"]:ch["r1"]]
         ops.gemm_nt(a1, lw["wo"].w, h_out, resid=h2, drop=dr(_dec_site(i, 5)))
         if i == Ld - 1:
@@ -912,8 +953,14 @@ class Engine:
         else:
             dy = dh
         wgrad("wo", f"d.dy.ffn.{i}", dy, ws[f"d.a1.{i}"], lw["wo"].g)
-        dpre = R(f"d.dpre.{i}" if defer else "d.dpre", f)
-        ops.gemm_nt(dy, lw["wo"].wt, dpre, aux=sl(ws[f"d.a1.{i}"]), aux_scale=1.0 / (1.0 - p))
+        if cfg.gated:      # dh = dy·Wo, then dpre = [da | db] of the gated activation (its dropout mask regenerated)
+            dha = R("d.dha", f)
+            ops.gemm_nt(dy, lw["wo"].wt, dha)
+            dpre = R(f"d.dpre.{i}" if defer else "d.dpre", 2 * f)
+            ops.gated_gelu_bwd(dha, sl(ws[f"d.pre.{i}"]), dpre, dr(_dec_site(i, 4)))
+        else:
+            dpre = R(f"d.dpre.{i}" if defer else "d.dpre", f)
+            ops.gemm_nt(dy, lw["wo"].wt, dpre, aux=sl(ws[f"d.a1.{i}"]), aux_scale=1.0 / (1.0 - p))
         wgrad("wi", f"d.dpre.{i}", dpre, ws[f"d.xn3.{i}"], lw["wi"].g)
         dxn = R("d.dxn", d)
         ops.gemm_nt(dpre, lw["wi"].wt, dxn)
@@ -1022,7 +1069,7 @@ class Engine:
         # (embedding → blocks → final norm per chain of samples; the LM head and the loss see all rows again)
         self._run_chains(chains, Ld, lambda i, ch: self._dec_layer_fwd(ws, i, ch, enc_out, kv, rel, T, S))
         logits = self._buf(ws, "d.logits", (Md, V), torch.float32)
-        ops.gemm_nt(dec_out, self.shared.w, logits, alpha=d ** -0.5)       # tied LM head × d_model^-0.5
+        ops.gemm_nt(dec_out, self.lm_head.w, logits, alpha=self.head_alpha)       # tied LM head × d_model^-0.5, or the untied head
         loss_buf = self._buf(ws, "d.loss", (2,), torch.float32)
         ops.ce_fwd_bwd(logits, ctx.labels, loss_buf, None)
         self.ctx = ctx
@@ -1036,14 +1083,16 @@ class Engine:
             a, b = self.by_name[first_block], self.by_name[last_block]
             self.grad_hook(a.off, b.off + -(-b.numel // ALIGN) * ALIGN)
 
-    def _ffn_bwd(self, lw, dh, a1, xn, h_in, rs, ln, p, drop_out, tmp, dw=None, dy_pre=None, nxt=None, role="d", slot=""):
+    def _ffn_bwd(self, lw, dh, a1, xn, h_in, rs, ln, p, drop_out, tmp, dw=None, dy_pre=None, nxt=None, role="d", slot="", pre=None,
+                 drop_act=None):
         """residual FFN sublayer backward; dh is updated in place to the gradient wrt the sublayer input.
         `dw`: list collecting the weight-gradient problems for one grouped launch (encoder layers with dropout: their
         operands live in per-layer scratch that stays untouched until the layer's backward is complete).
         `dy_pre`: dropout_bwd(dh) already written by the RMSNorm backward that produced dh; `nxt` = (buffer, dropout) asks
         this sublayer's RMSNorm backward to do the same for the next consumer (saves a pass over the residual gradient).
         `role` ("d" decoder / "e" encoder) names the scratch: by ROLE, never by row count — the unpadded encoder has a
-        different row count for almost every batch, and a size in the name would leave one dead buffer set per batch."""
+        different row count for almost every batch, and a size in the name would leave one dead buffer set per batch.
+        `pre` (gated-GELU feed-forward): the saved [a | b] product; `drop_act` the dropout of the activation."""
         ops = self.ops
         M, d = dh.shape
         f = a1.shape[1]
@@ -1057,8 +1106,18 @@ class Engine:
             dw.append((dy, a1, lw["wo"].g, 1.0))
         else:
             ops.gemm_tn(dy, a1, lw["wo"].g)
-        dpre = self._buf(tmp, f"{role}.dpre{slot}", (M, f))
-        ops.gemm_nt(dy, lw["wo"].wt, dpre, aux=a1, aux_scale=1.0 / (1.0 - p))   # ∘ [relu'>0] ∘ dropout
+        if pre is not None:
+            dpre = self._buf(tmp, f"{role}.dpre{slot}", (M, 2 * f))
+            fz = self._fuse_gated(dy, lw["wo"].wt, f)
+            if fz == "fused":      # dpre straight from the dY·Wo product's epilogue (bit-identical to the two launches below)
+                ops.gemm_nt_gated(dy, lw["wo"].wt, dpre, pre, drop_act, backward=True)
+            else:
+                dha = self._buf(tmp, f"{role}.dha", (M, f))
+                (ops.gemm_nt_four if fz else ops.gemm_nt)(dy, lw["wo"].wt, dha)
+                ops.gated_gelu_bwd(dha, pre, dpre, drop_act)
+        else:
+            dpre = self._buf(tmp, f"{role}.dpre{slot}", (M, f))
+            ops.gemm_nt(dy, lw["wo"].wt, dpre, aux=a1, aux_scale=1.0 / (1.0 - p))   # ∘ [relu'>0] ∘ dropout
         if dw is not None:
             dw.append((dpre, xn, lw["wi"].g, 1.0))
         else:
@@ -1091,17 +1150,17 @@ class Engine:
         # ---- loss + LM head ------------------------------------------------------------------
         dlog = self._buf(tmp, "dlogits", (Md, V))
         ops.ce_fwd_bwd(ws["d.logits"], ctx.labels, self._buf(tmp, "loss2", (2,), torch.float32), dlog, upstream)
-        alpha = d ** -0.5
+        alpha, head = self.head_alpha, self.lm_head
         dh = self._buf(tmp, "d.dh", (Md, d))
         dout = self._buf(tmp, "d.dxn", (Md, d))
         # K = vocabulary (32128) for an [Md, d] output of a handful of tiles: accumulate in fp32 with atomics so that the
         # library may split K over the idle CUs (gemm_nt_ring_kernel), then round once to the compute dtype
         dout32 = dout if dout.dtype == torch.float32 else self._buf(tmp, "d.dout32", (Md, d), torch.float32)
         if self.det:      # LAKO_DETERMINISTIC=1: one workgroup per output tile walks the whole vocabulary (no K-split, no atomics)
-            ops.gemm_nt(dlog, self.shared.wt, dout, alpha=alpha)
+            ops.gemm_nt(dlog, head.wt, dout, alpha=alpha)
         else:
             ops.zero_(dout32)
-            ops.gemm_nt(dlog, self.shared.wt, dout32, alpha=alpha, atomic=True)
+            ops.gemm_nt(dlog, head.wt, dout32, alpha=alpha, atomic=True)
             if dout32 is not dout:
                 ops.cast(dout32.view(-1), dout.view(-1))
         # (K = B·T rows, 378 tiles: one K-split; nothing else touches the embedding gradient until the embedding backward kernels later on
@@ -1110,7 +1169,9 @@ class Engine:
         # gradient accumulation — adds)
         one = -2 if self._g_fresh else -1
         self._g_fresh = False
-        ops.gemm_tn(dlog, ws["d.out"], self.shared.g, alpha=alpha, split_k=one)
+        ops.gemm_tn(dlog, ws["d.out"], head.g, alpha=alpha, split_k=one)
+        if head is not self.shared:
+            self._ready("lm_head", "lm_head")
         # every RMSNorm backward also writes dropout_bwd(dx) for the residual branch that consumes dx next (fused=True)
         fused = p > 0 and os.environ.get("LAKO_FUSE_DROP", "1") != "0"   # 0: separate dropout_apply launches (A/B)
         xa = ctx.xa
@@ -1190,7 +1251,8 @@ class Engine:
             # each and pay one fp32 atomic pass over the output per split
             dy_s = self._buf(tmp, "e.dy" + sl, (Me, d)) if fused else None
             self._ffn_bwd(lw, deh, ws[f"e.a1.{j}"], ws[f"e.xn2.{j}"], ws[f"e.h1.{j}"], ws[f"e.rs2.{j}"], lw["ln2"], p,
-                          dr(_enc_site(i, 3)), tmp, dw, dy_pre=dy_f, nxt=(dy_s, dr(_enc_site(i, 1))) if fused else None, role="e", slot=sl)
+                          dr(_enc_site(i, 3)), tmp, dw, dy_pre=dy_f, nxt=(dy_s, dr(_enc_site(i, 1))) if fused else None, role="e", slot=sl,
+                          pre=ws[f"e.pre.{j}"] if cfg.gated else None, drop_act=dr(_enc_site(i, 2)))
             dy = deh
             if p > 0:
                 dy = dy_s if fused else self._buf(tmp, "e.dy", (Me, d))
@@ -1316,6 +1378,7 @@ class Engine:
         c1, qc, c2 = (self._buf(ws, f"g.{n}", (B, inner)) for n in ("c1", "qc", "c2"))
         st = self._buf(ws, "g.st", (B, H, 1, 4), torch.float32)
         a1 = self._buf(ws, "g.a1", (B, f))
+        pre = self._buf(ws, "g.pre", (B, 2 * f)) if cfg.gated else None
         logits = self._buf(ws, "g.logits", (B, V), torch.float32)
         def step(t):
             """enqueue decode step t (reads nxt, writes seq[:, t + 1], nxt, done, ndone[t])"""
@@ -1356,14 +1419,17 @@ class Engine:
                         ops.xattn_context(xp, enc_out, xoff[0], xoff[1], xc)
                         ops.headbatch_nt(xc.view(xa.splits, B, 1, H, d), self._xw(i, "v"), c2.view(B, 1, H, dk))
                 ops.gemm_nt(c2, lw["co"].w, h2, resid=h1)
+                out1, act = (pre, {}) if cfg.gated else (a1, dict(relu=True))
                 if fz:
-                    ops.gemm_nt(h2, lw["wi"].w, a1, relu=True, **nrm(lw["ln3"].p))
+                    ops.gemm_nt(h2, lw["wi"].w, out1, **nrm(lw["ln3"].p), **act)
                 else:
                     ops.rmsnorm_fwd(h2, lw["ln3"].p, xn, rs, eps)
-                    ops.gemm_nt(xn, lw["wi"].w, a1, relu=True)
+                    ops.gemm_nt(xn, lw["wi"].w, out1, **act)
+                if cfg.gated:
+                    ops.gated_gelu_fwd(pre, a1, None)
                 ops.gemm_nt(a1, lw["wo"].w, h, resid=h2)
             ops.rmsnorm_fwd(h, self.dec_final.p, xn, rs, eps)
-            ops.gemm_nt(xn, self.shared.w, logits, alpha=d ** -0.5)
+            ops.gemm_nt(xn, self.lm_head.w, logits, alpha=self.head_alpha)
             ops.greedy_step(logits, seq, t + 1, nxt, done, ndone[t:t + 1], cfg.eos_token_id, cfg.pad_token_id)
 
         # A decode step is ≈130 dependent launches of a few µs each: the host's launch rate bounds the loop.  After one eager call

@@ -27,6 +27,7 @@ from .engine import Engine, build_layout, layout_sizes
 # transformers: HF5:899-901).  Ignored unless the config says `legacy_cross_bias` — then it is a parameter (config.py, engine.py)
 LEGACY_IGNORED = ("decoder.block.0.layer.1.EncDecAttention.relative_attention_bias.weight",)
 ALIASES = ("lm_head.weight", "encoder.embed_tokens.weight", "decoder.embed_tokens.weight")
+UNTIED_ALIASES = ALIASES[1:]        # an untied head (T5 v1.1 / Flan-T5) is a parameter of its own
 
 
 def wrapped_name(plain: str) -> str:
@@ -151,7 +152,9 @@ class FiDT5(nn.Module):
                     prm.normal_(0.0, 1.0)
                 elif plain.endswith(".q.weight"):
                     prm.normal_(0.0, (d * dk) ** -0.5)
-                elif plain.endswith(".k.weight") or plain.endswith(".v.weight") or plain.endswith("wi.weight"):
+                elif plain == "lm_head.weight":          # untied head: HF5 _init_weights, std factor · 1.0
+                    prm.normal_(0.0, 1.0)
+                elif plain.endswith(".k.weight") or plain.endswith(".v.weight") or plain.endswith(("wi.weight", "wi_0.weight", "wi_1.weight")):
                     prm.normal_(0.0, d ** -0.5)
                 elif plain.endswith(".o.weight"):
                     prm.normal_(0.0, (H * dk) ** -0.5)
@@ -248,7 +251,8 @@ class FiDT5(nn.Module):
     def state_dict(self, *args, **kwargs):
         sd = super().state_dict(*args, **kwargs)
         shared = sd["shared.weight"]
-        sd["lm_head.weight"] = shared
+        if self.config.tie_word_embeddings:
+            sd["lm_head.weight"] = shared
         sd[("encoder.encoder." if self._wrapped else "encoder.") + "embed_tokens.weight"] = shared
         sd["decoder.embed_tokens.weight"] = shared
         return sd
@@ -268,7 +272,7 @@ class FiDT5(nn.Module):
                                       "semantics) that this model ignores; load it with legacy_cross_bias=True (from_pretrained / "
                                       "--legacy_cross_bias) to reproduce the reference's numbers", stacklevel=2)
                     continue
-                if pk in ALIASES:
+                if pk in (ALIASES if self.config.tie_word_embeddings else UNTIED_ALIASES):
                     continue
                 if pk not in self._params_by_plain:
                     if strict:

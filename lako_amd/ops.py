@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import (EPI_ATOMIC, EPI_AUXMASK, EPI_NORM_A, EPI_RELU, EPI_RESID, LAKO_BF16, LAKO_F32, LAKO_FP8_E4M3, AttnBwd, AttnFwd, Dropout,
+from ._lib import (EPI_ATOMIC, EPI_AUXMASK, EPI_GATED, EPI_GATED_BWD, EPI_NORM_A, EPI_RELU, EPI_RESID, LAKO_BF16, LAKO_F32, LAKO_FP8_E4M3, AttnBwd, AttnFwd, Dropout,
                    GemmNT, LakoError, NO_DROP, check)
 
 
@@ -209,6 +209,45 @@ class HipOps:
         self._timed(f"gemm_nt{'_skinny' if M <= 256 else ''}.{p.in_dtype}{p.out_dtype}", 2.0 * M * N * K, go)
         return rc[0]
 
+    # ---- the gated-GELU feed-forward's products with their fused epilogues (LAKO_EPI_GATED / _BWD: gemm_nt4.h) ---------------------
+    @staticmethod
+    def gated_fused_ok(A, B, f):
+        """the conditions of lako_gemm_nt's fused gated epilogues that depend on the operands (contiguous bf16; the engine passes contiguous
+        [M, ·] buffers): f % 128 == 0, K % 128 == 0, K >= 256.  Anything else runs the plain product + lako_gated_gelu_fwd / _bwd."""
+        K = A.shape[1]
+        return A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and f % 128 == 0 and K % 128 == 0 and K >= 256 and \
+            A.is_contiguous() and B.is_contiguous()
+
+    def gemm_nt_four(self, A, B, Cm):
+        """Cm = A·Bᵀ on the 256-row four-wave tile — the kernel and K order of gemm_nt_gated's product, whatever the shape: the
+        two-launch form of a shape the fused epilogues take (LAKO_FUSE_GATED=0) multiplies exactly as the fused form does"""
+        old = self.tuning.nt_variant
+        self.tuning.nt_variant = 9
+        try:
+            self.gemm_nt(A, B, Cm)
+        finally:
+            self.tuning.nt_variant = old
+
+    def gemm_nt_gated(self, A, B, Cm, side, drop=None, backward=False):
+        """forward (backward=False): A = xn [M, d], B = [Wi0; Wi1] [2f, d] → Cm = pre [M, 2f] and side = h [M, f] =
+        lako_gated_gelu_fwd(pre, drop) in one launch.  backward: A = dy [M, d], B = Woᵀ [f, d] → Cm = dpre [M, 2f] =
+        lako_gated_gelu_bwd(bf16(A·Bᵀ), side = pre, drop); the product itself is not stored.  Bit-identical to the two-launch forms."""
+        M, K, lda = _rowmajor2d(A, "gemm_nt_gated A")
+        N, K2, ldb = _rowmajor2d(B, "gemm_nt_gated B")
+        f = N // 2 if not backward else N
+        if K != K2 or Cm.shape != (M, 2 * f) or side.shape != ((M, f) if not backward else (M, 2 * f)) or not Cm.is_contiguous() or \
+                not side.is_contiguous() or not (A.dtype == B.dtype == Cm.dtype == side.dtype):
+            raise LakoError(f"gemm_nt_gated: shape/dtype mismatch A{tuple(A.shape)} B{tuple(B.shape)} C{tuple(Cm.shape)} side{tuple(side.shape)}")
+        p = GemmNT()
+        p.A, p.B, p.C, p.aux = A.data_ptr(), B.data_ptr(), Cm.data_ptr(), side.data_ptr()
+        p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.ldaux = M, N, K, lda, ldb, 2 * f, side.stride(0)
+        p.in_dtype, p.out_dtype = _dt(A), _dt(Cm)
+        p.alpha, p.flags, p.aux_scale = 1.0, (EPI_GATED_BWD if backward else EPI_GATED), 1.0
+        p.drop = _drop(drop)
+        p.tuning = self._tuning_p
+        self._timed(f"gemm_nt_gated{'_bwd' if backward else ''}", 2.0 * M * N * K,
+                    lambda: check(self.lib.lako_gemm_nt(C.byref(p), self._stream()), "lako_gemm_nt (gated)"))
+
     def gemm_tn(self, A, B, Cm, *, alpha=1.0, split_k=0):
         K, M, lda = _rowmajor2d(A, "gemm_tn A")
         K2, N, ldb = _rowmajor2d(B, "gemm_tn B")
@@ -291,6 +330,32 @@ class HipOps:
 
     def dropout_apply(self, x, y, drop):
         self._timed("dropout_apply", 0.0, lambda: check(self.lib.lako_dropout_apply(_p(x), _p(y), x.numel(), _dt(x), _drop(drop), self._stream()), "lako_dropout_apply"))
+
+    # ---- gated-GELU feed-forward (T5 v1.1) -------------------------------------------------------
+    @staticmethod
+    def _gated_check(name, pre, x, f):
+        M = pre.shape[0]
+        if pre.dim() != 2 or pre.shape[1] != 2 * f or not pre.is_contiguous() or not x.is_contiguous() or x.shape != (M, f) or \
+                x.dtype != pre.dtype:
+            raise LakoError(f"{name}: pre must be a contiguous [M, 2f] tensor and h / dh a contiguous [M, f] one of its dtype, got "
+                            f"{tuple(pre.shape)} and {tuple(x.shape)}")
+        return M
+
+    def gated_gelu_fwd(self, pre, h, drop=None):
+        """h [M, f] = dropout(gelu_new(pre[:, :f]) ⊙ pre[:, f:])"""
+        f = h.shape[1]
+        M = self._gated_check("gated_gelu_fwd", pre, h, f)
+        self._timed("gated_gelu_fwd", 0.0, lambda: check(self.lib.lako_gated_gelu_fwd(_p(pre), _p(h), M, f, _dt(h), _drop(drop), self._stream()),
+                                                          "lako_gated_gelu_fwd"))
+
+    def gated_gelu_bwd(self, dh, pre, dpre, drop=None):
+        """dpre [M, 2f] = [da | db] of gated_gelu_fwd for the upstream gradient dh [M, f]"""
+        f = dh.shape[1]
+        M = self._gated_check("gated_gelu_bwd", pre, dh, f)
+        if dpre.shape != pre.shape or not dpre.is_contiguous() or dpre.dtype != pre.dtype:
+            raise LakoError("gated_gelu_bwd: dpre must match pre")
+        self._timed("gated_gelu_bwd", 0.0, lambda: check(self.lib.lako_gated_gelu_bwd(_p(dh), _p(pre), _p(dpre), M, f, _dt(dh), _drop(drop),
+                                                                                      self._stream()), "lako_gated_gelu_bwd"))
 
     # ---- relative position bias ---------------------------------------------------------------
     def relpos_expand(self, table, lut, rel):
