@@ -2,6 +2,7 @@
 """Headline benchmark: train samples/sec of the FiD reader (BASELINE.json metric) on N MI355X GPUs.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,12 +18,18 @@ tensors plus the collator's host-side passage lengths; the unpadded encoder's in
 index) is part of the timed step — nothing about a batch is cached across steps.
 
 Rank 0 prints ONE JSON line.  `value` = samples of all ranks ÷ the wall time of the K timed steps (barrier +
-synchronize on both sides, max over ranks); `median_step_ms` is the median of the per-step HIP-event times.  `roofline` is
-for the dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of its launches ÷ their HIP-event time measured live on
-one extra step after the timed region; `step_mfma_frac` is the whole step against the same peak.  `all_valid` is a second,
-shorter measurement of the same step with every passage at full length (nothing to skip: the pure-roofline variant).
-`cpu_baseline` times the CPU oracle (same algorithm, torch fp32 on the host cores) on a bounded sample of the same workload —
-a reported baseline, not the target.
+synchronize on both sides, max over ranks); `median_step_ms` is the median of the per-step HIP-event times.
+`roofline.step_mfma_frac` is the whole step against the dominant kernel's (the bf16 MFMA GEMM's) peak.
+
+A plain run does only that: set up, warm up, time the K steps, write --dump-outputs, print the line.  What takes runs of its
+own is behind --full:
+  * `roofline.achieved` / `frac` / `launches_per_step` / `avg_launch_us` (and `bf16_gemm` / `mx_quantize_ms_per_step` under
+    --fp8): algorithmic FLOPs of the dominant kernel's launches ÷ their HIP-event time measured live on one extra step after
+    the timed region (--breakdown runs that step too and prints its per-op table to stderr);
+  * `all_valid`: a second, shorter measurement of the same step with every passage at full length (nothing to skip: the
+    pure-roofline variant; --all-valid-steps 0 skips it);
+  * `cpu_baseline`: the CPU oracle (same algorithm, torch fp32 on the host cores) timed on a bounded sample of the same
+    workload — a reported baseline, not the target (--no-cpu-baseline skips it).
 """
 from __future__ import annotations
 
@@ -300,17 +307,20 @@ def main():
     ap.add_argument("--target-len", type=int, default=8)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--dropout", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement also run what takes runs of its own: the "
+                    "kernel-probe step behind roofline.achieved / frac, the all-passages-full measurement and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--all-valid", action="store_true", help="every passage has the full text_maxlength tokens (no padding to skip)")
     ap.add_argument("--cpu-batch", type=int, default=1)
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-warmup", type=int, default=2)
-    ap.add_argument("--all-valid-steps", type=int, default=10, help="timed steps of the second, all-passages-full measurement (0 = skip)")
-    ap.add_argument("--cpu-seconds", type=float, default=150.0, help="hard deadline for the CPU baseline leg")
+    ap.add_argument("--all-valid-steps", type=int, default=10, help="--full: timed steps of the second, all-passages-full measurement (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=150.0, help="--full: hard deadline for the CPU baseline leg")
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--fp8", action="store_true", help="MX block-scaled fp8 (e4m3 + E8M0 scales) forward GEMMs for the encoder's QKV / FFN-in "
                     "projections and the cross-K/V projection (BASELINE config 5); roofline then describes that kernel against the fp8 peak")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-op HIP-event breakdown to stderr")
+    ap.add_argument("--breakdown", action="store_true", help="run the kernel-probe step (as --full does) and print its per-op HIP-event "
+                    "breakdown to stderr")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last timed step computed (loss, "
                     "logits, gradient norm, a seeded sample of the updated fp32 weights) as DIR/<name>.npy, float32, <= 64 MB in all")
     args = ap.parse_args()
@@ -379,10 +389,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(all_valid, warmup, steps, capture=False):
-        """warm-up, then EXACTLY `steps` timed steps between two fences; one more step afterwards carries the per-launch
-        HIP-event probe (its event records would perturb the step they sit in).  capture: snapshot what the last timed step
-        returned (before the probe step changes the weights) into the result's "outputs"."""
+    def measure(all_valid, warmup, steps, capture=False, probe=False):
+        """warm-up, then EXACTLY `steps` timed steps between two fences.  probe: one more step afterwards carries the per-launch
+        HIP-event probe (its event records would perturb the step they sit in); without it "probe" is None and the per-kernel
+        figures are zero.  capture: snapshot what the last timed step returned (before a probe step changes the weights) into
+        the result's "outputs"."""
         batches = [synthetic_batch(B, N, L, T, cfg.vocab_size, seed=rank * 7919 + i, device=device, all_valid=all_valid,
                                    with_lengths=True) for i in range(NB)]
 
@@ -421,11 +432,14 @@ def main():
         elapsed = time.perf_counter() - t0
         outputs = snapshot_outputs(model, *last) if capture else None
         per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
-        ops.probe = []
-        step(warmup + steps)
-        torch.cuda.synchronize()
-        probe = ops.probe_summary()
-        ops.probe = None
+        if probe:
+            ops.probe = []
+            step(warmup + steps)
+            torch.cuda.synchronize()
+            probe = ops.probe_summary()
+            ops.probe = None
+        else:
+            probe = None
         if use_dist:
             t = torch.tensor([elapsed], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -438,24 +452,26 @@ def main():
                       for i in range(warmup, warmup + steps)) / (steps * B)
         fl_proj = sum(executed_train_flops(cfg, lens_all[i % NB] if unpadded else full, T, False)
                       for i in range(warmup, warmup + steps)) / (steps * B)
-        n_l, t_ms, f_tot = probe.get(dom, (0, 0.0, 0.0))
+        kernels = probe or {}
+        n_l, t_ms, f_tot = kernels.get(dom, (0, 0.0, 0.0))
         achieved = f_tot / (t_ms * 1e-3) / 1e12 if t_ms > 0 else 0.0
-        nb, tb, fb = probe.get("gemm_nt.11", (0, 0.0, 0.0))
+        nb, tb, fb = kernels.get("gemm_nt.11", (0, 0.0, 0.0))
         bf16_gemm = {"launches_per_step": nb, "achieved_tflops": round(fb / (tb * 1e-3) / 1e12, 1) if tb > 0 else 0.0,
                      "ms_per_step": round(tb, 3)}
-        mxq = probe.get("mx_quantize", (0, 0.0, 0.0))
+        mxq = kernels.get("mx_quantize", (0, 0.0, 0.0))
         return dict(outputs=outputs, bf16_gemm=bf16_gemm, mxq_ms=mxq[1], elapsed=elapsed, ms=elapsed / steps * 1e3, median_ms=per_step[len(per_step) // 2], host_ms=host_ms,
                     probe=probe, fl_exec=fl_exec, fl_proj=fl_proj, xattn=xattn, valid_frac=float(lens_all.double().mean()) / L, n_l=n_l, t_ms=t_ms,
                     achieved=achieved, value=world * B * steps / elapsed,
                     step_frac=world * B / (elapsed / steps) * fl_exec / 1e12 / (PEAK_BF16_TFLOPS * world if args.fp8 else peak * world))
 
-    main_run = measure(args.all_valid, args.warmup, args.steps, capture=args.dump_outputs is not None and rank == 0)
+    main_run = measure(args.all_valid, args.warmup, args.steps, capture=args.dump_outputs is not None and rank == 0,
+                       probe=args.full or args.breakdown)
     if main_run["outputs"] is not None:
         write_outputs(args.dump_outputs, main_run["outputs"])
     av_run = None
-    if not args.all_valid and args.all_valid_steps > 0:
-        av_run = measure(True, 3, args.all_valid_steps)
-    total = args.warmup + args.steps + 1 + (3 + args.all_valid_steps + 1 if av_run else 0)
+    if args.full and not args.all_valid and args.all_valid_steps > 0:
+        av_run = measure(True, 3, args.all_valid_steps, probe=True)
+    total = args.warmup + args.steps + (main_run["probe"] is not None) + (3 + args.all_valid_steps + 1 if av_run else 0)
     final_loss = float(loss_acc.item()) / total
 
     if rank == 0:
@@ -512,9 +528,13 @@ def main():
                                       f"{r['fl_proj'] / 1e9:.1f} GFLOP/sample" if r["xattn"] else "") + "); step_mfma_frac prices the executed FLOPs, nominal_step_frac = samples/s x train_gflop_per_sample / peak (SURVEY.md §8d's formula, "
                                       "which counts padded positions and the K/V projection)"},
         }
-        if args.fp8:
+        if r["probe"] is None:     # no probe step ran: no per-kernel figures on the line
+            for k in ("achieved", "frac", "launches_per_step", "avg_launch_us"):
+                del out["roofline"][k]
+        elif args.fp8:
             out["roofline"]["bf16_gemm"] = r["bf16_gemm"]          # the GEMMs that stay bf16 in the same run (backward, o / wo projections)
             out["roofline"]["mx_quantize_ms_per_step"] = round(r["mxq_ms"], 3)
+        if args.fp8:
             out["roofline"]["step_mfma_frac_note"] = "whole step priced against the bf16 peak (most FLOPs of the step still run in bf16)"
         if av_run is not None:
             out["all_valid"] = {"value": round(av_run["value"], 3), "unit": "samples/s", "steps": args.all_valid_steps, "warmup": 3,
@@ -529,7 +549,7 @@ def main():
                 tf = f / (t * 1e-3) / 1e12 if t > 0 and f > 0 else 0.0
                 print(f"  {k:16s} launches {n:4d}  {t:8.3f} ms  {100 * t / tot:5.1f}%  {tf:8.1f} TFLOP/s", file=sys.stderr)
             print(f"  sum of kernels {tot:.3f} ms vs step {r['ms']:.3f} ms", file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
     if use_dist:
         dist.barrier()

@@ -118,7 +118,7 @@ def test_bench_self_launch_relays_its_arguments():
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_last(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "small", "--batch", "2", "--n-passages", "3",
-                        "--seq-len", "64", "--steps", "2", "--warmup", "1", "--cpu-seconds", "20"], capture_output=True, text=True,
+                        "--seq-len", "64", "--steps", "2", "--warmup", "1", "--cpu-seconds", "20", "--full"], capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

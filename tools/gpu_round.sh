@@ -5,7 +5,7 @@
 # Steps (any number, in order; a step may be followed by ONE quoted argument where noted):
 #   tests "<pytest args>"   pytest -m gpu -x -q <args>            → $OUT/pytest.log
 #   smoke                   __graft_entry__.smoke()               → $OUT/smoke.log
-#   bench                   default `python bench.py`             → $OUT/bench.json
+#   bench                   `python bench.py --full`              → $OUT/bench.json
 #   quick                   bench.py --steps 20 --warmup 5, no CPU leg, with the per-op HIP-event breakdown → $OUT/bench_quick.json, breakdown.txt
 #   ab "<LAKO_TUNING a>|<LAKO_TUNING b>|…"   the quick bench once per tuning string → $OUT/ab_<i>.json (+ one summary line each)
 #   ops "<bench_ops args>"  tools/bench_ops.py <args>             → $OUT/bench_ops.txt (appended)
@@ -22,10 +22,10 @@ set -x
 TAG=${TAG:-round}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-QUICK="--no-cpu-baseline --all-valid-steps 0 --steps 20 --warmup 5"
+QUICK="--full --no-cpu-baseline --all-valid-steps 0 --steps 20 --warmup 5"
 step_tests() { ( time eval "timeout ${PYTEST_TIMEOUT:-2400} python -m pytest $1 -m gpu -x -q --durations=10" ) >> $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log; tail -4 $OUT/pytest.log; }
 step_smoke() { python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log; }
-step_bench() { ( time python bench.py ) > $OUT/bench.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench.json; }
+step_bench() { ( time python bench.py --full ) > $OUT/bench.json 2> $OUT/bench.err; cut -c1-300 $OUT/bench.json; }
 step_quick() { python bench.py $QUICK --breakdown > $OUT/bench_quick.json 2> $OUT/breakdown.txt; cut -c1-220 $OUT/bench_quick.json; cat $OUT/breakdown.txt; }
 step_ab() {
   local i=0
@@ -41,16 +41,16 @@ step_ab() {
 step_ops() { python tools/bench_ops.py $1 >> $OUT/bench_ops.txt 2>&1; tail -40 $OUT/bench_ops.txt; }
 step_trace() {
   cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-  rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o b -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --all-valid-steps 0 > $OUT/bench_under_rocprof.json 2> $OUT/prof.log
+  rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o b -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --all-valid-steps 0 > $OUT/bench_under_rocprof.json 2> $OUT/prof.log
   python tools/rocpd_stats.py /tmp/prof_$TAG/b_results.db > $OUT/bench_kernel_stats.csv
   python tools/rocpd_timeline.py /tmp/prof_$TAG/b_results.db 6 > $OUT/step_timeline.txt
   python tools/rocpd_timeline.py /tmp/prof_$TAG/b_results.db 6 --all > $OUT/step_sequence.txt
   head -30 $OUT/step_timeline.txt
 }
 step_c45() {
-  python bench.py --model large --n-passages 40 --batch 8 --no-cpu-baseline --all-valid-steps 0 --steps 15 --warmup 4 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-  python bench.py --model large --n-passages 100 --batch 8 --no-cpu-baseline --all-valid-steps 0 --steps 8 --warmup 3 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
-  python bench.py --model large --n-passages 100 --batch 8 --no-cpu-baseline --all-valid-steps 0 --steps 8 --warmup 3 --fp8 > $OUT/bench_c5_fp8.json 2> $OUT/bench_c5_fp8.err
+  python bench.py --model large --n-passages 40 --batch 8 --full --no-cpu-baseline --all-valid-steps 0 --steps 15 --warmup 4 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+  python bench.py --model large --n-passages 100 --batch 8 --full --no-cpu-baseline --all-valid-steps 0 --steps 8 --warmup 3 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+  python bench.py --model large --n-passages 100 --batch 8 --full --no-cpu-baseline --all-valid-steps 0 --steps 8 --warmup 3 --fp8 > $OUT/bench_c5_fp8.json 2> $OUT/bench_c5_fp8.err
   cut -c1-200 $OUT/bench_c4.json $OUT/bench_c5.json $OUT/bench_c5_fp8.json
 }
 step_generate() { python tools/generate_probe.py > $OUT/generate_probe.txt 2>&1; tail -2 $OUT/generate_probe.txt; }
@@ -58,7 +58,7 @@ step_pmcstep() {
   cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
   for p in mfma fetch write; do
     case $p in mfma) C="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE";; fetch) C="FETCH_SIZE";; write) C="WRITE_SIZE";; esac
-    rocprofv3 --pmc $C --output-format csv -d /tmp/pmcstep/$p -o p -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --all-valid-steps 0 > /tmp/pmcstep_$p.json 2>/dev/null
+    rocprofv3 --pmc $C --output-format csv -d /tmp/pmcstep/$p -o p -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --all-valid-steps 0 > /tmp/pmcstep_$p.json 2>/dev/null
   done
   python tools/pmc_step_totals.py /tmp/pmcstep 8 | tee $OUT/step_pmc_totals.txt
 }
