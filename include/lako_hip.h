@@ -207,7 +207,8 @@ int lako_rmsnorm_fwd(const void* x, const float* w, void* y, float* rstd, int64_
                      int dtype, lako_dropout_t drop, lako_stream_t stream);
 /* dx = (dres ? dres : 0) + rmsnorm_bwd(dropout_bwd(dy)); dw (fp32 [d]) += Σ_rows dy·x·rstd (atomics).
  * dx_drop (may be NULL): also written, = lako_dropout_apply(dx, drop_out) — the gradient entering the next residual branch
- * through ITS output dropout, produced in the same pass instead of a second read of dx */
+ * through ITS output dropout, produced in the same pass instead of a second read of dx.
+ * d % 8 == 0, d <= 4096 (d > 1024: 2 or 4 waves share a row; d <= 1024 runs the one-wave-per-row kernel as before). */
 int lako_rmsnorm_bwd(const void* dy, const void* x, const float* w, const float* rstd, const void* dres,
                      void* dx, float* dw, int64_t rows, int d, int dtype, lako_dropout_t drop, void* dx_drop,
                      lako_dropout_t drop_out, lako_stream_t stream);
@@ -242,7 +243,8 @@ int lako_relpos_reduce(const float* drel, const int32_t* lut, float* dtable, int
  * Used for encoder self-attention (bidirectional bias + key padding mask), decoder self-attention
  * (causal + unidirectional bias) and cross-attention over the concatenated n_passages·L encoder
  * states (key padding mask only).  bf16 / d_head 64 / <= 256 keys / no key mask / no causal mask / no score capture (the ragged
- * encoder self-attention of training) takes the fast path of csrc/attn_enc.hip; everything else the generic kernels. */
+ * encoder self-attention of training) takes the fast path of csrc/attn_enc.hip; everything else the generic kernels.
+ * d_head 32, 64 or 128 (T5-3B; generic kernels only), LAKO_E_UNSUPPORTED otherwise. */
 typedef struct {
   const void *q, *k, *v; /* element (b, t, h, c) at ptr + b*stride_b + t*stride_t + h*d_head + c */
   void* out;             /* same addressing with o_stride_* */

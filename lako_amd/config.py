@@ -37,8 +37,9 @@ class FiDConfig:
 
     @staticmethod
     def named(size: str, **over) -> "FiDConfig":
-        """t5-small / t5-base / t5-large dimensions (the `--model_size` flag, src/options.py:57), and the T5 v1.1 / Flan-T5 sizes
-        (gated-GELU feed-forward, untied LM head)."""
+        """t5-small / t5-base / t5-large / t5-3b dimensions (the `--model_size` flag, src/options.py:57), and the T5 v1.1 / Flan-T5
+        sizes up to xl (gated-GELU feed-forward, untied LM head).  11b / xxl are not offered: their optimizer state alone (~180 GB)
+        leaves no room for activations on one GPU."""
         v11 = dict(feed_forward_proj="gated-gelu", tie_word_embeddings=False)
         table = {
             "tiny": dict(vocab_size=64, d_model=32, d_kv=32, d_ff=64, num_layers=2, num_decoder_layers=2, num_heads=2),
@@ -48,6 +49,8 @@ class FiDConfig:
             "v1_1-small": dict(d_model=512, d_ff=1024, num_layers=8, num_decoder_layers=8, num_heads=6, **v11),
             "v1_1-base": dict(d_model=768, d_ff=2048, num_layers=12, num_decoder_layers=12, num_heads=12, **v11),
             "v1_1-large": dict(d_model=1024, d_ff=2816, num_layers=24, num_decoder_layers=24, num_heads=16, **v11),
+            "3b": dict(d_model=1024, d_kv=128, d_ff=16384, num_layers=24, num_decoder_layers=24, num_heads=32),
+            "v1_1-xl": dict(d_model=2048, d_ff=5120, num_layers=24, num_decoder_layers=24, num_heads=32, **v11),
         }
         if size not in table:
             raise ValueError(f"unknown model size {size!r}")

@@ -825,9 +825,16 @@ int lds_bytes_bwd(int ch, int R, bool merge) {
   return 2 * img_bytes<T, DK>(ch) + (3 * ch + 2 * R + 16 + 2 * OFFS_MAX + (merge ? 4 * 16 * DK : 0)) * 4;
 }
 
-inline int pick_chunk(int L) {
+// LDS-side rows per chunk: enough for L rows, at most CH_MAX, and — d_head 128, whose rows are 272 B (bf16) / 528 B (fp32) — no more
+// than the dynamic allocation of one workgroup holds.  32 rows always fit (R <= 4096: check_common), and at d_head 32 / 64 the chunk of
+// every shape that launched before is unchanged (those launches fit), so their results are too.
+constexpr int LDS_WG_MAX = 163840;   // gfx950: bytes of LDS one workgroup can allocate
+template <typename T, int DK, bool BWD>
+int pick_chunk(int L, int R, bool merge) {
   int ch = ((L + 31) / 32) * 32;
-  return ch > CH_MAX ? CH_MAX : ch;
+  if (ch > CH_MAX) ch = CH_MAX;
+  while (ch > 32 && (BWD ? lds_bytes_bwd<T, DK>(ch, R, merge) : lds_bytes_fwd<T, DK>(ch, R, merge)) > LDS_WG_MAX) ch -= 32;
+  return ch;
 }
 
 // raise the kernel's dynamic-LDS limit only when a launch needs more than any earlier one ON THIS DEVICE (`cur` is a per-instantiation
@@ -850,8 +857,8 @@ inline int pick_blocks_per_wg(int nblocks, int64_t bh) {
 
 template <typename T, int DK>
 int run_fwd(AttnArgs& a, hipStream_t s) {
-  a.chunk_rows = pick_chunk(a.Lk);
   const int nqb = (a.Lq + 15) / 16;
+  a.chunk_rows = pick_chunk<T, DK, false>(a.Lk, a.R, nqb == 1);
   a.blocks_per_wg = pick_blocks_per_wg(nqb, (int64_t)a.Bn * a.H);
   const int lds = lds_bytes_fwd<T, DK>(a.chunk_rows, a.R, nqb == 1);
   dim3 grid((nqb + a.blocks_per_wg - 1) / a.blocks_per_wg, a.H, a.Bn);
@@ -871,8 +878,8 @@ template <typename T, int DK>
 int run_bwd(AttnArgs& a, hipStream_t s) {
   {  // dQ pass
     AttnArgs q = a;
-    q.chunk_rows = pick_chunk(a.Lk);
     const int nqb = (a.Lq + 15) / 16;
+    q.chunk_rows = pick_chunk<T, DK, true>(a.Lk, a.R, nqb == 1);
     q.blocks_per_wg = pick_blocks_per_wg(nqb, (int64_t)a.Bn * a.H);
     q.bn_per_wg = 1;
 #ifdef LAKO_EXPERIMENTS   // timing experiments (bits 4 / 8 drop the bias-gradient flushes: wrong results) — never in the release library
@@ -880,7 +887,7 @@ int run_bwd(AttnArgs& a, hipStream_t s) {
 #else
     constexpr int dbg = 0;
 #endif
-    if ((a.drel || (dbg & 1)) && a.Lk <= CH_MAX) {
+    if ((a.drel || (dbg & 1)) && a.Lk <= q.chunk_rows) {
       // bias gradient: one query block per wave, several batch rows per workgroup (register accumulation of dS)
       q.blocks_per_wg = 4;
       const int64_t wgs = (int64_t)a.Bn * a.H * ((nqb + 3) / 4);
@@ -906,7 +913,7 @@ int run_bwd(AttnArgs& a, hipStream_t s) {
     AttnArgs k = a;
     k.bn_per_wg = 1;
     k.grid_x = 0;
-    k.chunk_rows = pick_chunk(a.Lq);
+    k.chunk_rows = pick_chunk<T, DK, true>(a.Lq, a.R, false);
     const int nkb = (a.Lk + 15) / 16;
     k.blocks_per_wg = pick_blocks_per_wg(nkb, (int64_t)a.Bn * a.H);
     const int lds = lds_bytes_bwd<T, DK>(k.chunk_rows, a.R, false);
@@ -923,8 +930,8 @@ int check_common(const char* fn, int Bn, int H, int Lq, int Lk, int d_head, int 
   if (!(Bn > 0 && H > 0 && Lq > 0 && Lk > 0)) { lako_set_error("%s: bad dims", fn); return LAKO_E_BADARG; }
   if (!(Bn < 65536 && H < 65536)) { lako_set_error("%s: Bn/H too large for the grid", fn); return LAKO_E_BADARG; }
   if (!(dtype == LAKO_F32 || dtype == LAKO_BF16)) { lako_set_error("%s: bad dtype", fn); return LAKO_E_BADARG; }
-  if (!(d_head == 32 || d_head == 64)) {
-    lako_set_error("%s: d_head=%d unsupported (32 or 64)", fn, d_head);
+  if (!(d_head == 32 || d_head == 64 || d_head == 128)) {
+    lako_set_error("%s: d_head=%d unsupported (32, 64 or 128)", fn, d_head);
     return LAKO_E_UNSUPPORTED;
   }
   const int esz = dtype == LAKO_F32 ? 4 : 2;
@@ -958,9 +965,11 @@ void set_drop(AttnArgs& a, const lako_dropout_t& d) {
 #define ATTN_DISPATCH(dtype, dhead, FN, args, s)                    \
   if ((dtype) == LAKO_BF16) {                                       \
     if ((dhead) == 64) FN<bf16_t, 64>(args, s);                     \
+    else if ((dhead) == 128) FN<bf16_t, 128>(args, s);              \
     else FN<bf16_t, 32>(args, s);                                   \
   } else {                                                          \
     if ((dhead) == 64) FN<float, 64>(args, s);                      \
+    else if ((dhead) == 128) FN<float, 128>(args, s);               \
     else FN<float, 32>(args, s);                                    \
   }
 

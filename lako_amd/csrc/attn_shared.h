@@ -1,4 +1,4 @@
-// Declarations shared by the attention kernels: attn.hip (generic: fp32 / bf16, d_head 32 / 64, causal, key-split cross-attention,
+// Declarations shared by the attention kernels: attn.hip (generic: fp32 / bf16, d_head 32 / 64 / 128, causal, key-split cross-attention,
 // score capture, any key count) and attn_enc.hip (fast path of the encoder self-attention: bf16, d_head 64, <= 256 keys).
 #pragma once
 #include <float.h>

@@ -196,7 +196,7 @@ struct Raw8<float> {
   }
 };
 
-// dx = dres + rstd*(w∘dy − x·rstd²·mean(w∘dy∘x));  dw += Σ_rows dy∘x·rstd.   d <= 1024.
+// dx = dres + rstd*(w∘dy − x·rstd²·mean(w∘dy∘x));  dw += Σ_rows dy∘x·rstd.   d <= 1024 (wider rows: rmsnorm_bwd_wide_kernel).
 // A wave walks its rows one at a time; all three operands of the NEXT row (dy, x, dres) are requested before the current row's
 // reduction, so a row costs one memory round trip that overlaps the previous row's arithmetic instead of two exposed ones (the first
 // version fetched dres only after the wave reduction: 3.6-4.6 TB/s).  dx may alias dres: a row is read and written by one wave only.
@@ -308,6 +308,139 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const T* dy, const T* 
     return;
   }
   for (int c = threadIdx.x; c < d; c += 256) atomicAdd(dw + c, red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+}
+
+// The same for 1024 < d <= 4096 (T5-3B's d_ff side is not normed; Flan-T5-XL's d_model is 2048): WPR = 2 or 4 waves share a row, each
+// covering 1024 columns with the two 512-column strips of rmsnorm_bwd_kernel, so a lane holds as many registers as there.  The row's
+// Σ w∘dy∘x is summed per wave, then over the row's waves in wave order through LDS (one barrier per row, double-buffered); every wave
+// of the workgroup walks the same number of row steps so that the barrier is uniform.  dw: the 4 waves' partials are summed per column
+// in wave order, then one atomic (or fixed-point add under LAKO_DETERMINISTIC) per column per workgroup, as there.
+template <typename T, int WPR>
+__global__ __launch_bounds__(256) void rmsnorm_bwd_wide_kernel(const T* dy, const T* x, const float* __restrict__ w,
+                                                               const float* __restrict__ rstd, const T* dres, T* dx,
+                                                               float* __restrict__ dw, int64_t rows, int d, DropDev dr,
+                                                               T* __restrict__ dx_drop, DropDev dr_out, int det) {
+  static_assert(WPR == 2 || WPR == 4, "2 or 4 waves per row");
+  constexpr int RPB = 4 / WPR;                       // rows per workgroup step
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int part = wave % WPR, rg = wave / WPR;      // this wave's 1024 columns of the row / its row within the step
+  const int cb = part * 1024;
+  const int64_t step = (int64_t)gridDim.x * RPB;
+  __shared__ float ssum[2][4];
+  float dwacc[2][8];
+  float wv[2][8];
+  const int c0 = cb + lane * 8, c1 = cb + 512 + lane * 8;
+  const bool has1 = c1 < d, has0 = c0 < d;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    int c = cb + it * 512 + lane * 8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { dwacc[it][i] = 0.f; wv[it][i] = 0.f; }
+    if (c < d) load8(w + c, wv[it]);
+  }
+  Raw8<T> ng[2], nx[2], nr[2];
+  float nrs = 0.f;
+  auto fetch = [&](int64_t row) {
+    if (row < rows) {
+      nrs = rstd[row];
+      const int64_t base = row * d;
+      if (has0) {
+        ng[0].load(dy + base + c0);
+        nx[0].load(x + base + c0);
+        if (dres) nr[0].load(dres + base + c0);
+      }
+      if (has1) {
+        ng[1].load(dy + base + c1);
+        nx[1].load(x + base + c1);
+        if (dres) nr[1].load(dres + base + c1);
+      }
+    }
+  };
+  const int64_t r_first = (int64_t)blockIdx.x * RPB;
+  fetch(r_first + rg);
+  int par = 0;
+  for (int64_t r0 = r_first; r0 < rows; r0 += step, par ^= 1) {
+    const int64_t row = r0 + rg;
+    const bool live = row < rows;
+    const float rs = nrs;
+    float g[2][8], xv[2][8], o[2][8];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) g[it][i] = xv[it][i] = o[it][i] = 0.f;
+      if (live && (it == 0 ? has0 : has1)) {
+        ng[it].get(g[it]);
+        nx[it].get(xv[it]);
+        if (dres) nr[it].get(o[it]);
+      }
+    }
+    fetch(row + step);
+    float s = 0.f;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      int c = cb + it * 512 + lane * 8;
+      if (live && c < d) {
+        bool kp[8];
+        if (dr.thresh) keep8(dr.key, (uint64_t)row * d + c, dr.thresh, kp);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if (dr.thresh) g[it][i] = kp[i] ? g[it][i] * dr.scale : 0.f;
+          s += wv[it][i] * g[it][i] * xv[it][i];
+          dwacc[it][i] += g[it][i] * xv[it][i] * rs;
+        }
+      }
+    }
+    s = wave_sum(s);
+    if (lane == 0) ssum[par][wave] = s;
+    __syncthreads();
+    s = 0.f;
+#pragma unroll
+    for (int p = 0; p < WPR; ++p) s += ssum[par][rg * WPR + p];
+    if (!live) continue;
+    const float k = rs * rs * rs * s / (float)d;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      int c = cb + it * 512 + lane * 8;
+      if (c < d) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[it][i] += rs * wv[it][i] * g[it][i] - xv[it][i] * k;
+        store8(dx + row * d + c, o[it]);
+        if (dx_drop) {
+          bool kp[8];
+          keep8(dr_out.key, (uint64_t)row * d + c, dr_out.thresh, kp);
+          float od[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) od[i] = kp[i] ? (float)(T)o[it][i] * dr_out.scale : 0.f;
+          store8(dx_drop + row * d + c, od);
+        }
+      }
+    }
+  }
+  // red[wave][local column]: column c = part·1024 + local of the waves rg·WPR + part, summed over rg
+  __shared__ float red[4][1024];
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    int c = cb + it * 512 + lane * 8;
+    if (c < d) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) red[wave][it * 512 + lane * 8 + i] = dwacc[it][i];
+    }
+  }
+  __syncthreads();
+  auto col_sum = [&](int c) {
+    float v = 0.f;
+#pragma unroll
+    for (int r = 0; r < RPB; ++r) v += red[r * WPR + (c >> 10)][c & 1023];
+    return v;
+  };
+  if (det) {
+    __shared__ int last;
+    for (int c = threadIdx.x; c < d; c += 256) lako_det::add(&lako_det_slots[c], col_sum(c));
+    if (lako_det::last_block(&lako_det_ticket, gridDim.x, &last))
+      for (int c = threadIdx.x; c < d; c += 256) dw[c] += lako_det::take(&lako_det_slots[c]);
+    return;
+  }
+  for (int c = threadIdx.x; c < d; c += 256) atomicAdd(dw + c, col_sum(c));
 }
 
 #ifdef LAKO_EXPERIMENTS   // round 2's kernel (dres fetched after the reduction, no prefetch) for A/B timing: LAKO_RMS_OLD=1
@@ -1114,7 +1247,7 @@ extern "C" int lako_rmsnorm_bwd(const void* dy, const void* x, const float* w, c
                                 void* dx, float* dw, int64_t rows, int d, int dtype, lako_dropout_t drop, void* dx_drop,
                                 lako_dropout_t drop_out, lako_stream_t stream) {
   CHECK_DTYPE("lako_rmsnorm_bwd", dtype);
-  LAKO_CHECK_ARG(rows > 0 && d > 0 && d % 8 == 0 && d <= 1024, "lako_rmsnorm_bwd: rows=%lld d=%d (d %% 8 == 0, d <= 1024)",
+  LAKO_CHECK_ARG(rows > 0 && d > 0 && d % 8 == 0 && d <= 4096, "lako_rmsnorm_bwd: rows=%lld d=%d (d %% 8 == 0, d <= 4096)",
                  (long long)rows, d);
   LAKO_CHECK_ALIGN(dy, 16);
   LAKO_CHECK_ALIGN(x, 16);
@@ -1123,6 +1256,23 @@ extern "C" int lako_rmsnorm_bwd(const void* dy, const void* x, const float* w, c
   LAKO_CHECK_ARG(!dx_drop || drop_out.p > 0.f, "lako_rmsnorm_bwd: dx_drop without a dropout");
   LAKO_CHECK_ALIGN(dx_drop, 16);
   DropDev dr = make_drop(drop), dr_out = make_drop(drop_out);
+  if (d > 1024) {   // 2 (d <= 2048) or 4 waves per row, same grid cap as below
+    const int wpr = d > 2048 ? 4 : 2;
+    const int64_t steps = (rows + 4 / wpr - 1) / (4 / wpr);
+    const int wgrid = (int)(steps < 768 ? steps : 768);
+    const int det = lako_det::on() ? 1 : 0;
+    if (wpr == 2) {
+      DISPATCH_T(dtype, hipLaunchKernelGGL((rmsnorm_bwd_wide_kernel<T, 2>), dim3(wgrid), dim3(256), 0, (hipStream_t)stream,
+                                           (const T*)dy, (const T*)x, w, rstd, (const T*)dres, (T*)dx, dw, rows, d, dr, (T*)dx_drop,
+                                           dr_out, det));
+    } else {
+      DISPATCH_T(dtype, hipLaunchKernelGGL((rmsnorm_bwd_wide_kernel<T, 4>), dim3(wgrid), dim3(256), 0, (hipStream_t)stream,
+                                           (const T*)dy, (const T*)x, w, rstd, (const T*)dres, (T*)dx, dw, rows, d, dr, (T*)dx_drop,
+                                           dr_out, det));
+    }
+    LAKO_LAUNCH_CHECK();
+    return LAKO_OK;
+  }
   int grid = rows_grid(rows);
   // 3 blocks per CU = the 12 waves the kernel's 148 registers allow: every wave resident from the start, each keeping its next row
   // in flight.  Measured at 64 k rows × 768, in place + dropout_bwd(dx) (run r03j, 491 MB per launch): round 2's kernel 101 µs; this

@@ -183,8 +183,8 @@ class _Ctx:
 
 class Engine:
     def __init__(self, cfg: FiDConfig, ops, device, dtype=torch.bfloat16, seed: int = 0, fp8: bool | None = None):
-        if cfg.d_kv not in (32, 64):
-            raise ValueError(f"d_kv={cfg.d_kv} unsupported by the attention kernels (32 or 64)")
+        if cfg.d_kv not in (32, 64, 128):
+            raise ValueError(f"d_kv={cfg.d_kv} unsupported by the attention kernels (32, 64 or 128)")
         if cfg.d_model % 8 or cfg.d_ff % 8 or cfg.vocab_size % 8:
             raise ValueError("d_model, d_ff and vocab_size must be multiples of 8")
         self.cfg, self.ops, self.device, self.dtype = cfg, ops, torch.device(device), dtype
@@ -226,6 +226,8 @@ class Engine:
             raise ValueError("fp8 GEMMs need the bf16 engine on the HIP op set")
         if self.fp8 and cfg.gated:
             raise ValueError("fp8 GEMMs (LAKO_FP8=1) are not implemented for the gated-GELU feed-forward (T5 v1.1 / Flan-T5)")
+        if self.fp8 and cfg.d_kv != 64:
+            raise ValueError(f"fp8 GEMMs (LAKO_FP8=1) are not implemented for d_kv={cfg.d_kv} (T5-3B); they need d_kv 64")
         self._w8: dict = {}      # block name → (e4m3 bytes [N, K], scales) of the weight shadow
 
     # ------------------------------------------------------------------------------------------
