@@ -2135,6 +2135,115 @@ static int* nt_queue_counters(hipStream_t stream) {
 // the 8-phase main loop of the 256² / 8-wave kernel (tuning nt_pp) needs two K-steps per tile
 inline int nt_pp_mode(const lako_tuning_t& tu, const NtArgs& a) { return tu.nt_pp && a.K >= 128 ? 1 : 0; }
 
+// ---- rules that several launchers share, each stated once ---------------------------------------------------------------------
+// Tile ids walk bands of group_m tile-rows once the output is `min_tiles_n` tile columns wide: narrow outputs (≤ 7 tile columns) already
+// give an XCD a compact block; a negative knob forces |value| on every shape (tests).
+// Measured at 48 000 rows (profiles/r02g_gemm_group_m_traffic.txt): banding takes the wi projection's L2 misses (FETCH_SIZE) from
+// 217 to 163 MiB-units per launch with no change in time (244 → 241 µs) — the L2-miss traffic is not what bounds the kernel —
+// and the QKV projection from 185 to 178 µs at unchanged misses
+inline int nt_group_m(const lako_tuning_t& tu, int tiles_n, int min_tiles_n = 8) {
+  return tu.nt_group_m < 0 ? -tu.nt_group_m : (tiles_n >= min_tiles_n ? tu.nt_group_m : 0);
+}
+
+// NtArgs::dephase as the tuning asks for it: (phases << 16) | ticks, 0 = lockstep start
+inline int nt_dephase_word(const lako_tuning_t& tu) { return tu.nt_dephase > 0 ? ((tu.nt_dephase_n << 16) | (tu.nt_dephase & 0xffff)) : 0; }
+
+// TILE HEIGHT of the four-wave kernels (round 6).  A launch walks its tiles in rounds of 256 (one workgroup per CU), a partly filled round
+// costs a whole one, and a tile costs ≈ 4.5 µs + nk · (step256 for 256 rows | step192 for 192 rows) (nk = K-steps): true when the rounds
+// of 192-row tiles cost less.  bf16 (K-steps of 64): 1.32 / 0.99 µs, fitted to profiles/r06c_nt4_probe.txt — the K loop is MFMA-bound,
+// so three quarters of the rows take three quarters of the K-step; MX fp8 (K-steps of 128): 1.6 / 1.25 µs.
+// 47 757 × 768 outputs: 561 tiles of 256 rows = 3 rounds, 747 of 192 rows = 3 shorter ones.
+inline bool nt4_prefers_192(int M, int N, int nk, double step256, double step192) {
+  const int tn = cdiv(N, 256);
+  const double c8 = (double)cdiv((int64_t)cdiv(M, 256) * tn, 256) * (4.5 + step256 * nk);
+  const double c6 = (double)cdiv((int64_t)cdiv(M, 192) * tn, 256) * (4.5 + step192 * nk);
+  return c6 < c8;
+}
+
+// What the epilogue of the four-wave kernels (nt4_epilogue: gemm_nt4_kernel and gemm_nt4_mx_kernel, bf16 output) takes, and the 32-bit
+// offsets both kernels form; elem_bytes = size of an A / B element.  A call that fails this must not reach them: they IGNORE what they do
+// not implement.  Every epilogue but the atomic one and the fused norm (the callers' rules); a residual OR an aux operand (16-byte aligned
+// rows), not both.
+inline bool nt4_epilogue_ok(const NtArgs& a, int elem_bytes) {
+  if (a.N % 8 != 0 || a.ldc % 8 != 0 || reinterpret_cast<uintptr_t>(a.C) % 16 != 0 || (int64_t)256 * std::max(a.lda, a.ldb) * elem_bytes >= (1ll << 31))
+    return false;
+  // epilogues built into the kernels: alpha alone; {ReLU, dropout}; residual with or without dropout; the aux mask alone (all with alpha = 1)
+  const int side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
+  if (a.alpha != 1.0f && (a.flags != 0 || a.drop_thresh != 0)) return false;
+  if (a.drop_thresh != 0 && (uint64_t)(a.row0 + a.M + 256) * (uint64_t)a.N >= (1ull << 34)) return false;      // dropout quads are indexed in 32 bits
+  if (side == (LAKO_EPI_RESID | LAKO_EPI_AUXMASK)) return false;
+  if (side && (a.flags & LAKO_EPI_RELU)) return false;
+  if (side == LAKO_EPI_AUXMASK && a.drop_thresh != 0) return false;
+  if (side == LAKO_EPI_RESID && (a.ldr % 8 != 0 || reinterpret_cast<uintptr_t>(a.resid) % 16 != 0 || (int64_t)128 * a.ldr * 2 >= (1ll << 31))) return false;
+  if (side == LAKO_EPI_AUXMASK && (a.ldaux % 8 != 0 || reinterpret_cast<uintptr_t>(a.aux) % 16 != 0 || (int64_t)128 * a.ldaux * 2 >= (1ll << 31))) return false;
+  if ((int64_t)128 * a.ldc * 2 >= (1ll << 31)) return false;      // (32-bit offsets inside a wave's region)
+  return true;
+}
+
+// the four-wave hand-scheduled bf16 kernels (gemm_nt4.h): bf16 in and out, whole 128-byte K-slices in pairs
+template <typename T, typename TO>
+bool nt4_ok(const NtArgs& a) {
+  return sizeof(T) == 2 && sizeof(TO) == 2 && a.K % 128 == 0 && a.K >= 256 && !(a.flags & (LAKO_EPI_ATOMIC | LAKO_EPI_NORM_A)) && nt4_epilogue_ok(a, 2);
+}
+
+// 288-row tiles (MT = 9): bf16 in and out, static tile order (the QUEUE instantiations are 256-row)
+template <typename T, typename TO>
+bool nt288_ok(const NtArgs& a, const lako_tuning_t& tu) {
+  return sizeof(T) == 2 && sizeof(TO) == 2 && !(a.flags & LAKO_EPI_ATOMIC) && !tu.nt_queue;
+}
+
+// gemm_nt_skinny_kernel (bf16 operands): K in whole steps of 32 up to max_k (4 096; 1 024 for the fused norm, whose K-steps are all resident
+// in a wave), 16-byte rows everywhere, 32-bit operand offsets, no atomic epilogue
+inline bool nt_skinny_fits(const NtArgs& a, int max_k) {
+  return a.K % 32 == 0 && a.K >= 128 && a.K <= max_k && a.N % 8 == 0 && (int64_t)a.M * a.lda * 2 < (1ll << 31) && (int64_t)a.N * a.ldb * 2 < (1ll << 31) &&
+         a.lda % 8 == 0 && a.ldb % 8 == 0 && a.ldc % 8 == 0 && !(a.flags & LAKO_EPI_ATOMIC) &&
+         (!(a.flags & LAKO_EPI_RESID) || (a.ldr % 8 == 0 && reinterpret_cast<uintptr_t>(a.resid) % 16 == 0)) &&
+         (!(a.flags & LAKO_EPI_AUXMASK) || (a.ldaux % 8 == 0 && reinterpret_cast<uintptr_t>(a.aux) % 16 == 0)) &&
+         reinterpret_cast<uintptr_t>(a.A) % 16 == 0 && reinterpret_cast<uintptr_t>(a.B) % 16 == 0 && reinterpret_cast<uintptr_t>(a.C) % 16 == 0;
+}
+// … and when it is the kernel to take: forced (variant 5), or very skinny (the decoder: M <= 256 rows) when the choice is the library's
+inline bool nt_skinny_wanted(const NtArgs& a, const lako_tuning_t& tu) {
+  return tu.nt_variant == 5 || (tu.nt_variant < 0 && tu.nt_skinny && a.M <= 256 && a.N <= 4096);
+}
+
+// the fields of NtArgs that come straight from the caller's struct (the launchers fill in the rest)
+NtArgs nt_args_from(const lako_gemm_nt_t* p) {
+  NtArgs a{};
+  a.A = (const char*)p->A;
+  a.B = (const char*)p->B;
+  a.C = (char*)p->C;
+  a.resid = (const char*)p->resid;
+  a.aux = (const char*)p->aux;
+  a.M = (int)p->M;
+  a.N = (int)p->N;
+  a.K = (int)p->K;
+  a.lda = p->lda;
+  a.ldb = p->ldb;
+  a.ldc = p->ldc;
+  a.ldr = p->ldr;
+  a.ldaux = p->ldaux;
+  a.alpha = p->alpha;
+  a.aux_scale = p->aux_scale;
+  a.flags = p->flags;
+  a.drop_thresh = p->drop.p > 0.f ? lako_drop_thresh(p->drop.p) : 0u;
+  a.drop_scale = p->drop.p > 0.f ? 1.0f / (1.0f - p->drop.p) : 1.0f;
+  a.drop_key = lako_drop_key(p->drop.seed, p->drop.site);
+  return a;
+}
+
+// rows [r0, M) of a problem as a problem of its own (the tail launch)
+template <typename T, typename TO>
+NtArgs nt_rows_from(NtArgs a, int64_t r0) {
+  a.M -= (int)r0;
+  a.row0 += r0;
+  a.A += r0 * a.lda * (int64_t)sizeof(T);
+  a.C += r0 * a.ldc * (int64_t)sizeof(TO);
+  if (a.resid) a.resid += r0 * a.ldr * (int64_t)sizeof(TO);
+  if (a.aux) a.aux += r0 * a.ldaux * (int64_t)sizeof(T);
+  return a;
+}
+
+// ---- NT launchers: one kernel family each; they fill in the launch-dependent fields of NtArgs ---------------------------------------
 template <typename T, typename TO, int WM, int WN, int MT, int NT, bool SIDE = false, bool QUEUE = false, bool PP = false>
 void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
   constexpr int BM = WM * MT * 16, BN = WN * NT * 16, NW_ = WM * WN, BUF_ = (BM + BN) * TKB;
@@ -2149,11 +2258,7 @@ void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
   a.glds = tu.nt_glds && (int64_t)BM * std::max(a.lda, a.ldb) * (int64_t)sizeof(T) < (1ll << 31);   // 32-bit row offsets inside a tile
   a.store_aux = (int64_t)256 * a.ldc * 2 < (1ll << 31) ? tu.nt_store_aux : 0;   // tile-relative 32-bit store offsets
   a.debug = tu.nt_debug;
-  // narrow outputs (≤ 7 tile columns) already give an XCD a compact block; a negative knob forces |value| on every shape (tests).
-  // Measured at 48 000 rows (profiles/r02g_gemm_group_m_traffic.txt): banding takes the wi projection's L2 misses (FETCH_SIZE) from
-  // 217 to 163 MiB-units per launch with no change in time (244 → 241 µs) — the L2-miss traffic is not what bounds the kernel —
-  // and the QKV projection from 185 to 178 µs at unchanged misses
-  a.group_m = tu.nt_group_m < 0 ? -tu.nt_group_m : (a.tiles_n >= 8 ? tu.nt_group_m : 0);
+  a.group_m = nt_group_m(tu, a.tiles_n);
   // measured (tools/bench_ops.py --variants 2,32): +6…12 % on plain stores, a LOSS when a residual / aux operand must
   // be fetched in the row-major layout too — those keep the accumulator-layout epilogue
   a.wide_epi = tu.nt_wide_epi && !(a.flags & (LAKO_EPI_ATOMIC | LAKO_EPI_RESID | LAKO_EPI_AUXMASK)) && a.N % 8 == 0 &&
@@ -2168,14 +2273,11 @@ void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
   // DEPHASE: every other workgroup of an XCD starts 1 µs late when the workgroups walk several tiles.  Measured (tools/bench_ops.py
   // --dephase 0,100,…): [64000,768]×[2304,768] 287 → 250 µs, o+res 140 → 134, wi 374 → 366, long launches unchanged; the size of
   // the delay (1…16 µs) and the number of phases (2, 4, 8) do not matter — the lockstep start is what costs.
-  a.dephase = (tu.nt_dephase > 0 && a.tiles_m * a.tiles_n > grid) ? ((tu.nt_dephase_n << 16) | (tu.nt_dephase & 0xffff)) : 0;
+  a.dephase = a.tiles_m * a.tiles_n > grid ? nt_dephase_word(tu) : 0;
   if constexpr (QUEUE) {
     a.queue = nt_queue_counters(s);
     // (several K-steps per tile to cover the ticket's round trip, several tiles per workgroup to be of any use, a persistent grid)
-    if (!a.queue || a.K * (int)sizeof(T) <= TKB || a.tiles_m * a.tiles_n <= grid || !tu.nt_persistent) {
-      launch_nt_cfg<T, TO, WM, WN, MT, NT, SIDE, false>(a, tu, s);
-      return;
-    }
+    if (!a.queue || a.K * (int)sizeof(T) <= TKB || a.tiles_m * a.tiles_n <= grid || !tu.nt_persistent) return launch_nt_cfg<T, TO, WM, WN, MT, NT, SIDE, false>(a, tu, s);
   } else {
     a.queue = nullptr;
 #ifdef LAKO_EXPERIMENTS
@@ -2185,10 +2287,15 @@ void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
   hipLaunchKernelGGL((gemm_nt_kernel<T, TO, WM, WN, MT, NT, SIDE, QUEUE, PP>), dim3(grid), dim3(WM * WN * 64), LDS, s, a);
 }
 
-// 288-row tiles (MT = 9): bf16 in and out, static tile order (the QUEUE instantiations are 256-row)
-template <typename T, typename TO>
-bool nt288_ok(const NtArgs& a, const lako_tuning_t& tu) {
-  return sizeof(T) == 2 && sizeof(TO) == 2 && !(a.flags & LAKO_EPI_ATOMIC) && !tu.nt_queue;
+// the 256-column tile on 8 waves with or without the LDS-staged side operand; 256-row tiles (bf16 in and out) have the ticket-queue and the
+// eight-phase instantiations too
+template <typename T, typename TO, int MT, bool SIDE>
+void launch_nt_256_side(const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
+  if constexpr (MT == 8 && sizeof(T) == 2 && sizeof(TO) == 2) {
+    if (tu.nt_queue) return launch_nt_cfg<T, TO, 2, 4, 8, 4, SIDE, true>(a, tu, s);
+    if (nt_pp_mode(tu, a)) return launch_nt_cfg<T, TO, 2, 4, 8, 4, SIDE, false, true>(a, tu, s);
+  }
+  launch_nt_cfg<T, TO, 2, 4, MT, 4, SIDE>(a, tu, s);
 }
 
 // the 256² kernel, with the LDS-staged side operand where the epilogue has exactly one (bf16 in and out, 16-B aligned rows)
@@ -2200,55 +2307,39 @@ void launch_nt_256(const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
     const int64_t ld = side == LAKO_EPI_RESID ? a.ldr : a.ldaux;
     if (tu.nt_side_lds && (side == LAKO_EPI_RESID || side == LAKO_EPI_AUXMASK) && !(a.flags & LAKO_EPI_ATOMIC) && a.N % 8 == 0 &&
         a.ldc % 8 == 0 && ld % 8 == 0 && reinterpret_cast<uintptr_t>(a.C) % 16 == 0 && reinterpret_cast<uintptr_t>(sp) % 16 == 0 &&
-        (int64_t)256 * a.ldc * 2 < (1ll << 31) && (int64_t)256 * ld * 2 < (1ll << 31)) {
-      if (MT == 8 && tu.nt_queue) launch_nt_cfg<T, TO, 2, 4, 8, 4, true, true>(a, tu, s);
-      else if (MT == 8 && nt_pp_mode(tu, a)) launch_nt_cfg<T, TO, 2, 4, 8, 4, true, false, true>(a, tu, s);
-      else launch_nt_cfg<T, TO, 2, 4, MT, 4, true>(a, tu, s);
-      return;
-    }
-    if (MT == 8 && tu.nt_queue) {
-      launch_nt_cfg<T, TO, 2, 4, 8, 4, false, true>(a, tu, s);
-      return;
-    }
-    if (MT == 8 && nt_pp_mode(tu, a)) {
-      launch_nt_cfg<T, TO, 2, 4, 8, 4, false, false, true>(a, tu, s);
-      return;
-    }
+        (int64_t)256 * a.ldc * 2 < (1ll << 31) && (int64_t)256 * ld * 2 < (1ll << 31))
+      return launch_nt_256_side<T, TO, MT, true>(a, tu, s);
   }
-  launch_nt_cfg<T, TO, 2, 4, MT, 4>(a, tu, s);
+  launch_nt_256_side<T, TO, MT, false>(a, tu, s);
 }
 
-// the four-wave hand-scheduled kernels (gemm_nt4.h): bf16 in and out, whole 128-byte K-slices in pairs, every epilogue but the atomic one
-// and the fused norm; a residual OR an aux operand (16-byte aligned rows), not both
-template <typename T, typename TO>
-bool nt4_ok(const NtArgs& a) {
-  if (sizeof(T) != 2 || sizeof(TO) != 2 || a.K % 128 != 0 || a.K < 256 || (a.flags & (LAKO_EPI_ATOMIC | LAKO_EPI_NORM_A)) || a.N % 8 != 0 || a.ldc % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(a.C) % 16 != 0 || (int64_t)256 * std::max(a.lda, a.ldb) * 2 >= (1ll << 31))
-    return false;
-  // epilogues built into the kernels: alpha alone; {ReLU, dropout}; residual with or without dropout; the aux mask alone (all with alpha = 1)
-  const int side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
-  if (a.alpha != 1.0f && (a.flags != 0 || a.drop_thresh != 0)) return false;
-  if (a.drop_thresh != 0 && (uint64_t)(a.row0 + a.M + 256) * (uint64_t)a.N >= (1ull << 34)) return false;      // dropout quads are indexed in 32 bits
-  if (side == (LAKO_EPI_RESID | LAKO_EPI_AUXMASK)) return false;
-  if (side && (a.flags & LAKO_EPI_RELU)) return false;
-  if (side == LAKO_EPI_AUXMASK && a.drop_thresh != 0) return false;
-  if (side == LAKO_EPI_RESID && (a.ldr % 8 != 0 || reinterpret_cast<uintptr_t>(a.resid) % 16 != 0 || (int64_t)128 * a.ldr * 2 >= (1ll << 31))) return false;
-  if (side == LAKO_EPI_AUXMASK && (a.ldaux % 8 != 0 || reinterpret_cast<uintptr_t>(a.aux) % 16 != 0 || (int64_t)128 * a.ldaux * 2 >= (1ll << 31))) return false;
-  if ((int64_t)128 * a.ldc * 2 >= (1ll << 31)) return false;      // (32-bit offsets inside a wave's region)
-  return true;
+// one four-wave instantiation on a persistent grid of at most one workgroup per CU (a template on the kernel: LAKO_SET_MAX_LDS keeps one
+// flag per expansion, so one per instantiation)
+template <int MT, bool SIDE, int EPI = 0>
+void launch_nt4_kernel(const NtArgs& a, hipStream_t s) {
+  const int grid = std::min(a.tiles_m * a.tiles_n, 256);
+  LAKO_SET_MAX_LDS((&gemm_nt4_kernel<MT, SIDE, EPI>), nt4::LDS_BYTES);
+  hipLaunchKernelGGL((gemm_nt4_kernel<MT, SIDE, EPI>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);
 }
+
+// … and one of the MX fp8 form (gemm_nt4_mx.h; lako_gemm_nt_mx)
+template <int MT, bool SIDE>
+void launch_nt4_mx_kernel(const MxArgs& m, hipStream_t s) {
+  const int grid = std::min(m.nt.tiles_m * m.nt.tiles_n, 256);
+  LAKO_SET_MAX_LDS((&gemm_nt4_mx_kernel<MT, SIDE>), nt4::LDS_BYTES);
+  hipLaunchKernelGGL((gemm_nt4_mx_kernel<MT, SIDE>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, m);
+}
+
+// the four-wave kernels on (32 · MT)-row tiles.  The caller has checked nt4_ok.
 template <int MT>
 void launch_nt4(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
-  const bool side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
   a.tiles_m = cdiv(a.M, MT * 32);
   a.tiles_n = cdiv(a.N, 256);
-  a.group_m = tu.nt_group_m < 0 ? -tu.nt_group_m : (a.tiles_n >= 8 ? tu.nt_group_m : 0);
-  int grid = a.tiles_m * a.tiles_n;
-  if (grid > 256) grid = 256;
+  a.group_m = nt_group_m(tu, a.tiles_n);
   // no start offsets between the workgroups: with this loop every offset costs at the end of the launch what it saves in the store
   // phases (tools/gemm_nt4_dephase.py, profiles/r06d_nt4_dephase.txt: lockstep is the fastest of nine settings on all five shapes)
   a.dephase = 0;
-  if (tu.nt_debug & 256) a.dephase = tu.nt_dephase > 0 ? ((tu.nt_dephase_n << 16) | (tu.nt_dephase & 0xffff)) : 0;      // (A/B hook: tools/gemm_nt4_dephase.py)
+  if (tu.nt_debug & 256) a.dephase = nt_dephase_word(tu);      // (A/B hook: tools/gemm_nt4_dephase.py)
   a.debug = tu.nt_debug;
   a.queue = nullptr;
   // gemm_nt_four = 1: the dropout epilogues without a side operand straight from the accumulator layout (gemm_nt4.h), 3: through the LDS
@@ -2257,26 +2348,12 @@ void launch_nt4(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
 #ifdef LAKO_EXPERIMENTS
   if (tu.nt_debug & 64) a.queue = reinterpret_cast<int*>(lako_exp_nt_stamp_buffer());
 #endif
-  const bool relu = a.flags & LAKO_EPI_RELU, drop = a.drop_thresh != 0;
-  const int epi = (!side && drop && a.epi_direct) ? (relu ? 2 : 1) : 0;
-#define LAKO_NT4_DIRECT(E)                                                                                    \
-  case E:                                                                                                     \
-    LAKO_SET_MAX_LDS((&gemm_nt4_kernel<MT, false, E>), nt4::LDS_BYTES);                                       \
-    hipLaunchKernelGGL((gemm_nt4_kernel<MT, false, E>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);        \
-    return;
-  switch (epi) {
-    LAKO_NT4_DIRECT(1)
-    LAKO_NT4_DIRECT(2)
-    default: break;
+  if (a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK)) return launch_nt4_kernel<MT, true>(a, s);
+  if (a.drop_thresh != 0 && a.epi_direct) {
+    if (a.flags & LAKO_EPI_RELU) return launch_nt4_kernel<MT, false, 2>(a, s);
+    return launch_nt4_kernel<MT, false, 1>(a, s);
   }
-#undef LAKO_NT4_DIRECT
-  if (side) {
-    LAKO_SET_MAX_LDS((&gemm_nt4_kernel<MT, true>), nt4::LDS_BYTES);
-    hipLaunchKernelGGL((gemm_nt4_kernel<MT, true>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);
-  } else {
-    LAKO_SET_MAX_LDS((&gemm_nt4_kernel<MT, false>), nt4::LDS_BYTES);
-    hipLaunchKernelGGL((gemm_nt4_kernel<MT, false>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);
-  }
+  launch_nt4_kernel<MT, false>(a, s);
 }
 
 // the fused gated-GELU epilogues (LAKO_EPI_GATED / _BWD, gemm_nt4.h EPI 3 / 4) on the 256-row four-wave tile.  The caller (lako_gemm_nt)
@@ -2300,202 +2377,199 @@ void launch_nt4_gated(NtArgs a, hipStream_t s) {
   a.queue = nullptr;
   a.epi_direct = 0;
   a.row0 = 0;
-  int grid = a.tiles_m * a.tiles_n;
-  if (grid > 256) grid = 256;
-  if (a.flags == LAKO_EPI_GATED) {
-    LAKO_SET_MAX_LDS((&gemm_nt4_kernel<8, false, 3>), nt4::LDS_BYTES);
-    hipLaunchKernelGGL((gemm_nt4_kernel<8, false, 3>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);
-  } else {
-    LAKO_SET_MAX_LDS((&gemm_nt4_kernel<8, false, 4>), nt4::LDS_BYTES);
-    hipLaunchKernelGGL((gemm_nt4_kernel<8, false, 4>), dim3(grid), dim3(256), nt4::LDS_BYTES, s, a);
+  if (a.flags == LAKO_EPI_GATED) launch_nt4_kernel<8, false, 3>(a, s);
+  else launch_nt4_kernel<8, false, 4>(a, s);
+}
+
+// very skinny (the decoder): (16 · TB)² tiles, K split over the workgroup's eight waves — see gemm_nt_skinny_kernel.  One instantiation per
+// tile size and per bucket of K-steps of 32 a wave unrolls (4, 8 or 16: K <= 4 096); only the 64² tile's 128 KiB of LDS need the attribute.
+template <typename TO, int MAXS, int TB>
+void launch_nt_skinny_steps(const NtArgs& a, hipStream_t s) {
+  constexpr int LDS = 8 * (TB * 16) * (TB * 16) * 4;
+  if constexpr (LDS > 64 * 1024) LAKO_SET_MAX_LDS((&gemm_nt_skinny_kernel<TO, 8, MAXS, TB>), LDS);
+  hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, MAXS, TB>), dim3(cdiv(a.N, TB * 16), cdiv(a.M, TB * 16)), dim3(512), LDS, s, a);
+}
+template <typename TO, int TB>
+void launch_nt_skinny(const NtArgs& a, hipStream_t s) {
+  const int per = cdiv(a.K / 32, 8);
+  if (per <= 4) launch_nt_skinny_steps<TO, 4, TB>(a, s);
+  else if (per <= 8) launch_nt_skinny_steps<TO, 8, TB>(a, s);
+  else launch_nt_skinny_steps<TO, 16, TB>(a, s);
+}
+// RMSNorm of A in the fragments: K <= 1024 (all K-steps of a wave resident), 32² tiles
+template <typename TO>
+void launch_nt_skinny_norm(const NtArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 4, 2, true>), dim3(cdiv(a.N, 32), cdiv(a.M, 32)), dim3(512), 8 * 4096 + 8 * 32 * 4, s, a);
+}
+
+// skinny: at most one 128² tile per CU → the 4-slot ring hides the global→LDS latency inside the workgroup
+template <typename T, typename TO>
+void launch_nt_ring(NtArgs b, hipStream_t s) {
+  LAKO_SET_MAX_LDS((&gemm_nt_ring_kernel<T, TO>), RING_NST * RING_STAGE);
+  b.tiles_m = cdiv(b.M, RING_BM);
+  b.tiles_n = cdiv(b.N, RING_BM);
+  b.debug = 0;
+  const int tiles = b.tiles_m * b.tiles_n, nk_all = cdiv(b.K * (int)sizeof(T), TKB);
+  b.split_k = 1;
+  // a few tiles with a very long K (LM-head backward: 6 tiles × 502 K-steps) would run on 6 CUs: with fp32 atomic
+  // accumulation the K range may be cut into pieces of >= 8 K-steps over idle CUs (alpha is linear, no other epilogue)
+  if (b.flags == LAKO_EPI_ATOMIC && sizeof(TO) == 4 && tiles < 128 && nk_all >= 32)
+    b.split_k = std::max(1, std::min(256 / tiles, nk_all / 8));
+  b.k_chunk = cdiv(nk_all, b.split_k) * TKB;
+  b.split_k = cdiv(nk_all * TKB, b.k_chunk);
+  hipLaunchKernelGGL((gemm_nt_ring_kernel<T, TO>), dim3(tiles * b.split_k), dim3(256), RING_NST * RING_STAGE, s, b);
+}
+
+// ---- the NT plan: which kernel runs which rows.  nt_plan reads its arguments and nothing else — no HIP call, no launch — and launch_nt
+// carries the plan out, so nothing is in flight when a call is refused -------------------------------------------------------------------
+enum NtKernel {
+  NT_REFUSED = 0,     // no kernel takes the call
+  NT_FOUR,            // gemm_nt4_kernel, `rows` = 192 | 256 (launch_nt4)
+  NT_EIGHT,           // gemm_nt_kernel on 8 waves, `rows` = 192 | 256 | 288 by 256 columns (launch_nt_256)
+  NT_EIGHT_256x128,   // … 256 × 128 tiles (variant 1)
+  NT_FOUR_BY_128,     // … 256² on 4 waves of 128² (variant 6)
+  NT_128,             // … 128² on 4 waves
+  NT_RING,            // gemm_nt_ring_kernel
+  NT_SKINNY,          // gemm_nt_skinny_kernel, `rows` = tile side 16 | 32 | 64
+  NT_SKINNY_NORM,     // … with the RMSNorm of A formed in the fragments (LAKO_EPI_NORM_A)
+};
+struct NtPlan {
+  NtKernel kernel;     // runs rows [head_rows, M): all of them unless there is a head
+  int rows;
+  int64_t head_rows;   // > 0 (TAIL SPLIT): rows [0, head_rows) go to NT_EIGHT with head_tile-row tiles first
+  int head_tile;
+};
+
+// the kernel for variant v (tuning gemm_nt_variant, or what nt_plan made of "auto") on the rows of `a`; kernels refuse what they do not take
+// by handing the call on: skinny → ring, four-wave / 192- / 288-row tiles → the eight-wave 256² kernel
+template <typename T, typename TO>
+NtPlan nt_plan_variant(const NtArgs& a, int v, const lako_tuning_t& tu) {
+  constexpr bool BF_IN = sizeof(T) == 2, BF = BF_IN && sizeof(TO) == 2;
+  const bool auto_pick = tu.nt_variant < 0;
+  // a CU pulls ≈45 GB/s through its L1 whatever the other CUs do, so the bytes have to be spread over many CUs: 32² tiles
+  // (4 × the workgroups of 64² tiles, half the operand bytes each) — measured on the whole training step: 64² 50.4 ms,
+  // 32² 49.4 ms, 16² 49.3 ms ("gemm_nt_skinny" 2 / 3 / 4 force them)
+  if (BF_IN && nt_skinny_fits(a, 4096) && nt_skinny_wanted(a, tu)) return {NT_SKINNY, tu.nt_skinny == 4 ? 16 : tu.nt_skinny == 2 ? 64 : 32};
+  if (v == 4 || v == 5 || (auto_pick && tu.nt_ring && (int64_t)cdiv(a.M, RING_BM) * cdiv(a.N, RING_BM) <= 256)) return {NT_RING};
+  if ((v == 3 || v == 9) && !nt4_ok<T, TO>(a)) v = 2;
+  if ((v == 7 || v == 8) && !BF) v = 2;
+  switch (v) {
+    case 2: return {NT_EIGHT, 256};
+    case 7: return {NT_EIGHT, 192};
+    case 8: return {NT_EIGHT, nt288_ok<T, TO>(a, tu) ? 288 : 256};
+    case 9: return {NT_FOUR, 256};
+    case 3: return {NT_FOUR, 192};
+    case 6: return {BF_IN ? NT_FOUR_BY_128 : NT_128};   // EXPERIMENT: 256x256 on 4 waves of 128x128 (hipBLASLt's MT256x256x64 MIWT8_8 shape)
+    case 1: return {NT_EIGHT_256x128};
+    default: return {NT_128};
   }
 }
 
 template <typename T, typename TO>
-int launch_nt(const NtArgs& a_in, const lako_tuning_t& tu, hipStream_t s) {
-  NtArgs a = a_in;
-  int v = tu.nt_variant;
+NtPlan nt_plan(const NtArgs& a, const lako_tuning_t& tu) {
+  constexpr bool BF_IN = sizeof(T) == 2, BF = BF_IN && sizeof(TO) == 2;
   if (a.flags & LAKO_EPI_NORM_A) {
-    // the norm is formed by the M <= 256 kernel only: decide BEFORE any planning or launch (round 5, ADVICE: with a tail plan the head
-    // rows used to be launched un-normalised before the flag was refused) — the conditions of the skinny branch below, restated
-    bool ok = false;
-    if constexpr (sizeof(T) == 2) {
-      ok = a.K % 32 == 0 && a.K >= 128 && a.K <= 1024 && a.N % 8 == 0 && (int64_t)a.M * a.lda * 2 < (1ll << 31) && (int64_t)a.N * a.ldb * 2 < (1ll << 31) &&
-           a.lda % 8 == 0 && a.ldb % 8 == 0 && a.ldc % 8 == 0 && !(a.flags & LAKO_EPI_ATOMIC) &&
-           (!(a.flags & LAKO_EPI_RESID) || (a.ldr % 8 == 0 && reinterpret_cast<uintptr_t>(a.resid) % 16 == 0)) &&
-           (!(a.flags & LAKO_EPI_AUXMASK) || (a.ldaux % 8 == 0 && reinterpret_cast<uintptr_t>(a.aux) % 16 == 0)) &&
-           reinterpret_cast<uintptr_t>(a.A) % 16 == 0 && reinterpret_cast<uintptr_t>(a.B) % 16 == 0 && reinterpret_cast<uintptr_t>(a.C) % 16 == 0 &&
-           (v == 5 || (v < 0 && tu.nt_skinny && a.M <= 256 && a.N <= 4096));
+    // the norm is formed by the M <= 256 kernel only, and only with every K-step of a wave resident (round 5, ADVICE: with a tail plan the
+    // head rows used to be launched un-normalised before the flag was refused)
+    return {BF_IN && nt_skinny_fits(a, 1024) && nt_skinny_wanted(a, tu) ? NT_SKINNY_NORM : NT_REFUSED, 32};
+  }
+  if (tu.nt_variant >= 0) return nt_plan_variant<T, TO>(a, tu.nt_variant, tu);
+  const int tn = cdiv(a.N, 256);
+  const int64_t t256 = (int64_t)cdiv(a.M, 256) * tn;
+  // ROUND 6: the four-wave kernels, once there is a round of the chip of their tiles
+  if (tu.nt_four && !tu.nt_queue && nt4_ok<T, TO>(a) && t256 >= 256) return {NT_FOUR, nt4_prefers_192(a.M, a.N, a.K / 64, 1.32, 0.99) ? 192 : 256};
+  // big tiles once there is enough work to fill the chip with them (>= 1 tile per CU), else 128x128
+  if (t256 < 256 || !BF_IN) return nt_plan_variant<T, TO>(a, 0, tu);
+  if (t256 == 256) return nt_plan_variant<T, TO>(a, 2, tu);
+  // TAIL SPLIT.  256 persistent workgroups walk the 256² tiles in rounds; t256 = 564 (an unpadded batch of ≈48 k
+  // tokens × 768 columns) means 2 full rounds and a third with 52 tiles on 52 CUs: 3 tile-times for 2.2 of work.
+  // The rows of the full rounds go to the 256² kernel, the remaining rows to a second launch with 128² tiles
+  // (4 × as many, 2 workgroups per CU): ≈2.35 tile-times.  Only when the last round would be less than half full.
+  // TILE HEIGHT (round 3).  The same launch with 192-row tiles (the kernel's MT = 6 instantiation: ≈0.8 of a 256-row tile's time —
+  // three quarters of the FLOPs at 17 % more operand bytes per FLOP) can land on a whole number of rounds where the 256-row tiles
+  // do not: 47 757 rows × 768 columns are 747 tiles = 2.92 rounds → 3 × 0.8 = 2.4 tile-times and NO tail launch, against 2 + ≈0.7.
+  // Both plans are priced in 256-row tile-times and the cheaper one runs — when "gemm_nt_tile192" is 1.  It is 0 by default:
+  // measured (profiles/r03e_gemm_tile192.txt, 47 757 rows) a 192-row tile takes ≈0.93 of a 256-row tile's time, not 0.8 — the
+  // K-step is bound by the L2 → LDS path, whose bytes per tile fall by an eighth only — so three rounds of them (72.9 / 235 /
+  // 172 µs at K = 768 / 3072 / 2304) lose to two rounds + tail (71.4 / 228 / 165 µs).  Variant 7 forces the tile (tests).
+  struct Rounds { double cost; int64_t full_rows; bool tail; };
+  auto price = [&](int bm, double tile_time) {
+    const int64_t tiles = (int64_t)cdiv(a.M, bm) * tn;
+    const int64_t rounds = tiles / 256;
+    const int64_t full_rows = rounds * 256 / tn;                   // tile-rows covered by the full rounds
+    const int64_t rest = tiles - full_rows * tn;                   // tiles left for the last round
+    if (rest == 0) return Rounds{rounds * tile_time, full_rows, false};
+    // (nt_tail_split: 1 = split when the last round would be less than half full; a value > 1 is the threshold in 256² tiles)
+    if (tu.nt_tail_split && rest < (tu.nt_tail_split > 1 ? tu.nt_tail_split : 128) && full_rows > 0 && !(a.flags & LAKO_EPI_ATOMIC)) return Rounds{rounds * tile_time + 0.7, full_rows, true};
+    return Rounds{(rounds + 1) * tile_time, full_rows, false};
+  };
+  Rounds best = price(256, 1.0);
+  int bm = 256;
+  if (BF && tu.nt_tile192) {
+    const Rounds r192 = price(192, 0.8);
+    if (r192.cost < 0.97 * best.cost) {
+      best = r192;
+      bm = 192;
     }
-    if (!ok) return LAKO_E_BADARG;
   }
-  if (v < 0 && tu.nt_four && !tu.nt_queue && nt4_ok<T, TO>(a) && (int64_t)cdiv(a.M, 256) * cdiv(a.N, 256) >= 256) {
-    // ROUND 6: the four-wave kernels.  A launch walks its tiles in rounds of 256 (one workgroup per CU), a partly filled round costs a
-    // whole one, and a tile costs ≈ 4.5 µs + nk · (1.32 µs for 256 rows | 0.99 µs for 192 rows) (nk = K-steps; fitted to
-    // profiles/r06c_nt4_probe.txt — the K loop is MFMA-bound, so three quarters of the rows take three quarters of the K-step): take the
-    // height whose rounds cost less.  47 757 × 768 outputs: 561 tiles of 256 rows = 3 rounds, 747 of 192 rows = 3 shorter ones.
-    const int nk = a.K / 64, tn = cdiv(a.N, 256);
-    const double c8 = (double)cdiv((int64_t)cdiv(a.M, 256) * tn, 256) * (4.5 + 1.32 * nk);
-    const double c6 = (double)cdiv((int64_t)cdiv(a.M, 192) * tn, 256) * (4.5 + 0.99 * nk);
-    if (c6 < c8) launch_nt4<6>(a, tu, s);
-    else launch_nt4<8>(a, tu, s);
-    return 0;
+  // 288-ROW TILES (round 4, MT = 9; profiles/r04h_gemm_tile_height.txt).  The other direction pays: a 288-row tile takes ≈1.13–1.16 of a
+  // 256-row tile's time for 1.125 of its work, and 47 757 rows × 768 columns are 498 of them — two rounds at 97 % instead of two rounds +
+  // a 128²-tile tail launch: −10…−12 % per call on the three N = 768 gradient products of a layer, −1…−3 % at N = 2304 / 3072 (one round
+  // fewer).  144 accumulator registers: 243 VGPRs with the plain epilogues; with a side operand 288-row tiles need the 16-row side passes
+  // (launch_nt_256<…, 9>).
+  if (tu.nt_tile288 && nt288_ok<T, TO>(a, tu)) {
+    const Rounds r288 = price(288, tu.nt_tile288 >= 2 ? 1.0 + 0.01 * tu.nt_tile288 : 1.13);      // (values >= 2: the price in percent over a 256-row tile, A/B)
+    if (r288.cost < 0.99 * best.cost) {
+      best = r288;
+      bm = 288;
+    }
   }
-  if (v < 0) {
-    // big tiles once there is enough work to fill the chip with them (>= 1 tile per CU), else 128x128
-    const int tn = cdiv(a.N, 256);
-    const int64_t t256 = (int64_t)cdiv(a.M, 256) * tn;
-    v = (t256 >= 256 && sizeof(T) == 2) ? 2 : 0;
-    // TAIL SPLIT.  256 persistent workgroups walk the 256² tiles in rounds; t256 = 564 (an unpadded batch of ≈48 k
-    // tokens × 768 columns) means 2 full rounds and a third with 52 tiles on 52 CUs: 3 tile-times for 2.2 of work.
-    // The rows of the full rounds go to the 256² kernel, the remaining rows to a second launch with 128² tiles
-    // (4 × as many, 2 workgroups per CU): ≈2.35 tile-times.  Only when the last round would be less than half full.
-    // TILE HEIGHT (round 3).  The same launch with 192-row tiles (the kernel's MT = 6 instantiation: ≈0.8 of a 256-row tile's time —
-    // three quarters of the FLOPs at 17 % more operand bytes per FLOP) can land on a whole number of rounds where the 256-row tiles
-    // do not: 47 757 rows × 768 columns are 747 tiles = 2.92 rounds → 3 × 0.8 = 2.4 tile-times and NO tail launch, against 2 + ≈0.7.
-    // Both plans are priced in 256-row tile-times and the cheaper one runs — when "gemm_nt_tile192" is 1.  It is 0 by default:
-    // measured (profiles/r03e_gemm_tile192.txt, 47 757 rows) a 192-row tile takes ≈0.93 of a 256-row tile's time, not 0.8 — the
-    // K-step is bound by the L2 → LDS path, whose bytes per tile fall by an eighth only — so three rounds of them (72.9 / 235 /
-    // 172 µs at K = 768 / 3072 / 2304) lose to two rounds + tail (71.4 / 228 / 165 µs).  Variant 7 forces the tile (tests).
-    struct Plan { double cost; int64_t full_rows; bool tail; };
-    auto plan = [&](int bm, double tile_time) {
-      const int64_t tiles = (int64_t)cdiv(a.M, bm) * tn;
-      const int64_t rounds = tiles / 256;
-      const int64_t full_rows = rounds * 256 / tn;                   // tile-rows covered by the full rounds
-      const int64_t rest = tiles - full_rows * tn;                   // tiles left for the last round
-      if (rest == 0) return Plan{rounds * tile_time, full_rows, false};
-      // (nt_tail_split: 1 = split when the last round would be less than half full; a value > 1 is the threshold in 256² tiles)
-      if (tu.nt_tail_split && rest < (tu.nt_tail_split > 1 ? tu.nt_tail_split : 128) && full_rows > 0 && !(a.flags & LAKO_EPI_ATOMIC)) return Plan{rounds * tile_time + 0.7, full_rows, true};
-      return Plan{(rounds + 1) * tile_time, full_rows, false};
-    };
-    if (v == 2 && t256 > 256) {
-      Plan pl = plan(256, 1.0);
-      int bm = 256;
+  if (!best.tail) return nt_plan_variant<T, TO>(a, bm == 192 ? 7 : bm == 288 ? 8 : 2, tu);
+  // the tail: 128² tiles (round 4: 256 × 128 / 8-wave tiles for the tail measured +0.2 ms on the step) — or the ring / skinny kernel, as for
+  // any call of so few rows
+  NtPlan pl = nt_plan_variant<T, TO>(nt_rows_from<T, TO>(a, best.full_rows * bm), 0, tu);
+  pl.head_rows = best.full_rows * bm;
+  pl.head_tile = bm;
+  return pl;
+}
+
+template <typename T, typename TO>
+void launch_nt_kernel(NtKernel kernel, int rows, const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
+  switch (kernel) {
+    case NT_FOUR: return rows == 192 ? launch_nt4<6>(a, tu, s) : launch_nt4<8>(a, tu, s);
+    case NT_EIGHT:
       if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {
-        if (tu.nt_tile192) {
-          const Plan p192 = plan(192, 0.8);
-          if (p192.cost < 0.97 * pl.cost) {
-            pl = p192;
-            bm = 192;
-          }
-        }
-        // 288-ROW TILES (round 4, MT = 9; profiles/r04h_gemm_tile_height.txt).  The other direction pays: a 288-row tile takes ≈1.13–1.16 of a
-        // 256-row tile's time for 1.125 of its work, and 47 757 rows × 768 columns are 498 of them — two rounds at 97 % instead of two rounds +
-        // a 128²-tile tail launch: −10…−12 % per call on the three N = 768 gradient products of a layer, −1…−3 % at N = 2304 / 3072 (one round
-        // fewer).  144 accumulator registers: 243 VGPRs with the plain epilogues; with a side operand 288-row tiles need the 16-row side passes
-        // (launch_nt_256<…, 9>).
-        if (tu.nt_tile288 && !(a.flags & LAKO_EPI_ATOMIC) && nt288_ok<T, TO>(a, tu)) {
-          const Plan p288 = plan(288, tu.nt_tile288 >= 2 ? 1.0 + 0.01 * tu.nt_tile288 : 1.13);      // (values >= 2: the price in percent over a 256-row tile, A/B)
-          if (p288.cost < 0.99 * pl.cost) {
-            pl = p288;
-            bm = 288;
-          }
-        }
+        if (rows == 192) return launch_nt_256<T, TO, 6>(a, tu, s);
+        if (rows == 288) return launch_nt_256<T, TO, 9>(a, tu, s);
       }
-      if (pl.tail) {
-        NtArgs head = a;
-        head.M = (int)(pl.full_rows * bm);
-        if (bm == 192) {
-          if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) launch_nt_256<T, TO, 6>(head, tu, s);
-        } else if (bm == 288) {
-          if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) launch_nt_256<T, TO, 9>(head, tu, s);
-        } else {
-          launch_nt_256<T, TO>(head, tu, s);
-        }
-        const int64_t r0 = pl.full_rows * bm;
-        a.M -= (int)r0;
-        a.row0 += r0;
-        a.A += r0 * a.lda * (int64_t)sizeof(T);
-        a.C += r0 * a.ldc * (int64_t)sizeof(TO);
-        if (a.resid) a.resid += r0 * a.ldr * (int64_t)sizeof(TO);
-        if (a.aux) a.aux += r0 * a.ldaux * (int64_t)sizeof(T);
-        v = 0;      // the tail: 128² tiles (round 4: 256 × 128 / 8-wave tiles for the tail measured +0.2 ms on the step)
-      } else if (bm == 192) {
-        v = 7;
-      } else if (bm == 288) {
-        v = 8;
-      }
-    }
+      return launch_nt_256<T, TO>(a, tu, s);
+    case NT_EIGHT_256x128: return launch_nt_cfg<T, TO, 4, 2, 4, 4>(a, tu, s);
+    case NT_FOUR_BY_128: return launch_nt_cfg<T, TO, 2, 2, 8, 8>(a, tu, s);
+    case NT_128: return launch_nt_cfg<T, TO, 2, 2, 4, 4>(a, tu, s);
+    case NT_RING: return launch_nt_ring<T, TO>(a, s);
+    case NT_SKINNY:
+      if constexpr (sizeof(T) == 2) rows == 16 ? launch_nt_skinny<TO, 1>(a, s) : rows == 64 ? launch_nt_skinny<TO, 4>(a, s) : launch_nt_skinny<TO, 2>(a, s);
+      return;
+    case NT_SKINNY_NORM:
+      if constexpr (sizeof(T) == 2) launch_nt_skinny_norm<TO>(a, s);
+      return;
+    case NT_REFUSED: return;
   }
-  if ((v == 3 || v == 9) && !nt4_ok<T, TO>(a)) v = 2;   // (forced four-wave kernels: shapes / epilogues they do not take run on the eight-wave kernel)
-  if (v == 5 && sizeof(T) != 2) v = 4;
-  if constexpr (sizeof(T) == 2) {
-    // very skinny (the decoder): 64×64 tiles, K split over the workgroup's four waves — see gemm_nt_skinny_kernel
-    const bool fits = a.K % 32 == 0 && a.K >= 128 && a.K <= 4096 && a.N % 8 == 0 && (int64_t)a.M * a.lda * 2 < (1ll << 31) && (int64_t)a.N * a.ldb * 2 < (1ll << 31) && a.lda % 8 == 0 && a.ldb % 8 == 0 && a.ldc % 8 == 0 &&
-                      !(a.flags & LAKO_EPI_ATOMIC) && (!(a.flags & LAKO_EPI_RESID) || (a.ldr % 8 == 0 && reinterpret_cast<uintptr_t>(a.resid) % 16 == 0)) &&
-                      (!(a.flags & LAKO_EPI_AUXMASK) || (a.ldaux % 8 == 0 && reinterpret_cast<uintptr_t>(a.aux) % 16 == 0)) &&
-                      reinterpret_cast<uintptr_t>(a.A) % 16 == 0 && reinterpret_cast<uintptr_t>(a.B) % 16 == 0 &&
-                      reinterpret_cast<uintptr_t>(a.C) % 16 == 0;
-    if (fits && (v == 5 || (tu.nt_variant < 0 && tu.nt_skinny && a.M <= 256 && a.N <= 4096))) {
-      LAKO_SET_MAX_LDS((&gemm_nt_skinny_kernel<TO, 8, 4, 4>), 8 * 16384);
-LAKO_SET_MAX_LDS((&gemm_nt_skinny_kernel<TO, 8, 8, 4>), 8 * 16384);
-LAKO_SET_MAX_LDS((&gemm_nt_skinny_kernel<TO, 8, 16, 4>), 8 * 16384);
-      // a CU pulls ≈45 GB/s through its L1 whatever the other CUs do, so the bytes have to be spread over many CUs: 32² tiles
-      // (4 × the workgroups of 64² tiles, half the operand bytes each) — measured on the whole training step: 64² 50.4 ms,
-      // 32² 49.4 ms, 16² 49.3 ms ("gemm_nt_skinny" 2 / 3 / 4 force them)
-      const bool small = tu.nt_skinny != 2;
-      const int ts = small ? 32 : 64;
-      const dim3 grid(cdiv(a.N, ts), cdiv(a.M, ts));
-      const int per = cdiv(a.K / 32, 8);
-      if (a.flags & LAKO_EPI_NORM_A) {      // RMSNorm of A in the fragments: K <= 1024 (all K-steps of a wave resident), 32² tiles
-        if (per > 4) return LAKO_E_BADARG;
-        const dim3 g32(cdiv(a.N, 32), cdiv(a.M, 32));
-        hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 4, 2, true>), g32, dim3(512), 8 * 4096 + 8 * 32 * 4, s, a);
-        return 0;
-      }
-      if (tu.nt_skinny == 4) {
-        const dim3 g16(cdiv(a.N, 16), cdiv(a.M, 16));
-        if (per <= 4) hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 4, 1>), g16, dim3(512), 8 * 1024, s, a);
-        else if (per <= 8) hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 8, 1>), g16, dim3(512), 8 * 1024, s, a);
-        else hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 16, 1>), g16, dim3(512), 8 * 1024, s, a);
-      } else if (small) {
-        if (per <= 4) hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 4, 2>), grid, dim3(512), 8 * 4096, s, a);
-        else if (per <= 8) hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 8, 2>), grid, dim3(512), 8 * 4096, s, a);
-        else hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 16, 2>), grid, dim3(512), 8 * 4096, s, a);
-      } else {
-        if (per <= 4) hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 4, 4>), grid, dim3(512), 8 * 16384, s, a);
-        else if (per <= 8) hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 8, 4>), grid, dim3(512), 8 * 16384, s, a);
-        else hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, 16, 4>), grid, dim3(512), 8 * 16384, s, a);
-      }
-      return 0;
-    }
-    if (v == 5) v = 4;
+}
+
+// LAKO_E_BADARG: no kernel takes the call, and nothing was launched (tests: test_gemm_nt_norm_refused_before_any_launch)
+template <typename T, typename TO>
+int launch_nt(const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
+  const NtPlan pl = nt_plan<T, TO>(a, tu);
+  if (pl.kernel == NT_REFUSED) return LAKO_E_BADARG;
+  if (pl.head_rows > 0) {
+    NtArgs head = a;
+    head.M = (int)pl.head_rows;
+    launch_nt_kernel<T, TO>(NT_EIGHT, pl.head_tile, head, tu, s);
+    launch_nt_kernel<T, TO>(pl.kernel, pl.rows, nt_rows_from<T, TO>(a, pl.head_rows), tu, s);
+  } else {
+    launch_nt_kernel<T, TO>(pl.kernel, pl.rows, a, tu, s);
   }
-  if (a.flags & LAKO_EPI_NORM_A) return LAKO_E_BADARG;      // only the skinny kernel forms the norm in its fragments
-  if (v == 4 || (tu.nt_variant < 0 && tu.nt_ring && (int64_t)cdiv(a.M, RING_BM) * cdiv(a.N, RING_BM) <= 256)) {
-    // skinny: at most one 128² tile per CU → the 4-slot ring hides the global→LDS latency inside the workgroup
-    LAKO_SET_MAX_LDS((&gemm_nt_ring_kernel<T, TO>), RING_NST * RING_STAGE);
-    NtArgs b = a;
-    b.tiles_m = cdiv(a.M, RING_BM);
-    b.tiles_n = cdiv(a.N, RING_BM);
-    b.debug = 0;
-    const int tiles = b.tiles_m * b.tiles_n, nk_all = cdiv(a.K * (int)sizeof(T), TKB);
-    b.split_k = 1;
-    // a few tiles with a very long K (LM-head backward: 6 tiles × 502 K-steps) would run on 6 CUs: with fp32 atomic
-    // accumulation the K range may be cut into pieces of >= 8 K-steps over idle CUs (alpha is linear, no other epilogue)
-    if (a.flags == LAKO_EPI_ATOMIC && sizeof(TO) == 4 && tiles < 128 && nk_all >= 32)
-      b.split_k = std::max(1, std::min(256 / tiles, nk_all / 8));
-    b.k_chunk = cdiv(nk_all, b.split_k) * TKB;
-    b.split_k = cdiv(nk_all * TKB, b.k_chunk);
-    hipLaunchKernelGGL((gemm_nt_ring_kernel<T, TO>), dim3(tiles * b.split_k), dim3(256), RING_NST * RING_STAGE, s, b);
-    return 0;
-  }
-  if ((v == 7 || v == 8) && (sizeof(T) != 2 || sizeof(TO) != 2)) v = 2;
-  if (v == 2) launch_nt_256<T, TO>(a, tu, s);
-  else if (v == 7) {
-    if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) launch_nt_256<T, TO, 6>(a, tu, s);     // 192 x 256 tiles
-  } else if (v == 8) {
-    if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {                                          // 288 x 256 tiles
-      if (nt288_ok<T, TO>(a, tu)) launch_nt_256<T, TO, 9>(a, tu, s);
-      else launch_nt_256<T, TO>(a, tu, s);
-    }
-  } else if (v == 9 && nt4_ok<T, TO>(a)) {
-    launch_nt4<8>(a, tu, s);
-  } else if (v == 3 && nt4_ok<T, TO>(a)) {
-    launch_nt4<6>(a, tu, s);
-  } else if (v == 6 && sizeof(T) == 2) launch_nt_cfg<T, TO, 2, 2, 8, 8>(a, tu, s);   // EXPERIMENT: 256x256 on 4 waves of 128x128 (hipBLASLt's MT256x256x64 MIWT8_8 shape)
-  else if (v == 1) launch_nt_cfg<T, TO, 4, 2, 4, 4>(a, tu, s);
-  else launch_nt_cfg<T, TO, 2, 2, 4, 4>(a, tu, s);
   return 0;
 }
 
@@ -2504,6 +2578,21 @@ int launch_tn(const TnArgs& a, hipStream_t s) {
   LAKO_SET_MAX_LDS((&gemm_tn_kernel<T>), GEMM_LDS);
   hipLaunchKernelGGL((gemm_tn_kernel<T>), dim3(a.tiles_m * a.tiles_n * a.split_k), dim3(256), GEMM_LDS, s, a);
   return 0;
+}
+
+// the 256² weight-gradient kernels on `grid` workgroups: the four-wave kernel where it applies (tn4_ok), else the eight-wave one with its
+// K-steps by global_load_lds or by buffer loads
+void launch_tn256(const TnArgs& a, const lako_tuning_t& tu, int grid, hipStream_t s) {
+  if (tn4_ok(a, tu)) {
+    LAKO_SET_MAX_LDS((&gemm_tn4_kernel), tn4::LDS_BYTES);
+    hipLaunchKernelGGL(gemm_tn4_kernel, dim3(grid), dim3(256), tn4::LDS_BYTES, s, a);
+  } else if (a.glds && a.k_chunk % 64 == 0) {
+    LAKO_SET_MAX_LDS((&gemm_tn256_kernel<true>), 4 * TN2_IMG);
+    hipLaunchKernelGGL(gemm_tn256_kernel<true>, dim3(grid), dim3(512), 4 * TN2_IMG, s, a);
+  } else {
+    LAKO_SET_MAX_LDS((&gemm_tn256_kernel<false>), 4 * TN2_IMG);
+    hipLaunchKernelGGL(gemm_tn256_kernel<false>, dim3(grid), dim3(512), 4 * TN2_IMG, s, a);
+  }
 }
 
 }  // namespace
@@ -2537,27 +2626,7 @@ extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
     return LAKO_E_UNSUPPORTED;
   }
   LAKO_CHECK_ARG(p->drop.p >= 0.f && p->drop.p < 1.f, "lako_gemm_nt: dropout p out of range");
-  NtArgs a{};
-  a.row0 = 0;
-  a.A = (const char*)p->A;
-  a.B = (const char*)p->B;
-  a.C = (char*)p->C;
-  a.resid = (const char*)p->resid;
-  a.aux = (const char*)p->aux;
-  a.M = (int)p->M;
-  a.N = (int)p->N;
-  a.K = (int)p->K;
-  a.lda = p->lda;
-  a.ldb = p->ldb;
-  a.ldc = p->ldc;
-  a.ldr = p->ldr;
-  a.ldaux = p->ldaux;
-  a.alpha = p->alpha;
-  a.aux_scale = p->aux_scale;
-  a.flags = p->flags;
-  a.drop_thresh = p->drop.p > 0.f ? lako_drop_thresh(p->drop.p) : 0u;
-  a.drop_scale = p->drop.p > 0.f ? 1.0f / (1.0f - p->drop.p) : 1.0f;
-  a.drop_key = lako_drop_key(p->drop.seed, p->drop.site);
+  NtArgs a = nt_args_from(p);
   if (p->flags & LAKO_EPI_NORM_A) {
     if (p->in_dtype != LAKO_BF16) {
       lako_set_error("lako_gemm_nt: LAKO_EPI_NORM_A is implemented for bf16 operands only");
@@ -2617,49 +2686,43 @@ static int tn_pick_split(int tiles, int64_t K, int max_split) {
   return best;
 }
 
-static int tn_single(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
-                     int in_dtype, float alpha, int split_k, const lako_tuning_t* tuning, lako_stream_t stream, int rows_out);
-
-extern "C" int lako_gemm_tn(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda,
-                            int64_t ldb, int64_t ldc, int in_dtype, float alpha, int split_k, const lako_tuning_t* tuning,
-                            lako_stream_t stream) {
-  return tn_single(A, B, C, M, N, K, lda, ldb, ldc, in_dtype, alpha, split_k, tuning, stream, 0);
+// The operand rules of one TN problem, for lako_gemm_tn and for every item of lako_gemm_tn_grouped: `who` names the entry point in the
+// message, item >= 0 the item.  esz = bytes of an A / B element.
+static int tn_check_item(const char* who, int item, const lako_gemm_tn_item_t& p, int esz) {
+  auto fail = [&](int code, const char* what) {
+    if (item < 0) lako_set_error("%s: %s", who, what);
+    else lako_set_error("%s: item %d: %s", who, item, what);
+    return code;
+  };
+  if (!(p.a && p.b && p.c && p.M > 0 && p.N > 0)) return fail(LAKO_E_BADARG, "null operand / empty problem");
+  if ((p.M * esz) % 16 != 0 || (p.N * esz) % 16 != 0 || (p.lda * esz) % 16 != 0 || (p.ldb * esz) % 16 != 0)
+    return fail(LAKO_E_BADARG, "M/N/lda/ldb must make 16-byte rows");
+  // (voffset = row * ld_bytes must stay below 2^32 within one K-step: rows < 64)
+  if (p.M >= (1 << 30) || p.N >= (1 << 30) || (int64_t)64 * p.lda * esz >= (1ll << 31) || (int64_t)64 * p.ldb * esz >= (1ll << 31))
+    return fail(LAKO_E_BADARG, "dims / leading dimension too large");
+  if (reinterpret_cast<uintptr_t>(p.a) % 16 != 0) return fail(LAKO_E_ALIGN, "pointer a not 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(p.b) % 16 != 0) return fail(LAKO_E_ALIGN, "pointer b not 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(p.c) % 4 != 0) return fail(LAKO_E_ALIGN, "pointer c not 4-byte aligned");
+  if (p.rows_out < 0 || p.rows_out > p.M) return fail(LAKO_E_BADARG, "rows_out");
+  return LAKO_OK;
 }
 
-// rows_out: 0 = M, else only the first rows_out rows of C are written (lako_gemm_tn_item_t.rows_out)
-static int tn_single(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
-                     int in_dtype, float alpha, int split_k, const lako_tuning_t* tuning, lako_stream_t stream, int rows_out) {
-  const lako_tuning_t& tu = tuning ? *tuning : process_tuning();
-  LAKO_CHECK_ARG(M > 0 && N > 0 && K > 0, "lako_gemm_tn: bad dims");
+// one problem (lako_gemm_tn, and the items of a grouped call that the grouped 256² launch does not take)
+static int tn_single(const lako_gemm_tn_item_t& p, int64_t K, int in_dtype, int split_k, const lako_tuning_t& tu, hipStream_t s) {
+  LAKO_CHECK_ARG(p.M > 0 && p.N > 0 && K > 0, "lako_gemm_tn: bad dims");
   LAKO_CHECK_ARG(split_k >= -2, "lako_gemm_tn: split_k %d", split_k);
   const int out_mode = split_k < 0 ? -split_k : 0;      // -1: exclusive read-modify-write, -2: overwrite (one K-split either way)
   if (split_k < 0) split_k = 1;
   if (lako_det::on() && split_k == 0) split_k = 1;      // LAKO_DETERMINISTIC=1: K-splits meet by float atomics in arrival order — one contributor
   LAKO_CHECK_ARG(in_dtype == LAKO_F32 || in_dtype == LAKO_BF16, "lako_gemm_tn: bad in_dtype");
+  LAKO_CHECK_ARG(K < (1 << 30), "lako_gemm_tn: dims too large");
   const int esz = in_dtype == LAKO_F32 ? 4 : 2;
-  LAKO_CHECK_ARG((M * esz) % 16 == 0 && (N * esz) % 16 == 0 && (lda * esz) % 16 == 0 && (ldb * esz) % 16 == 0,
-                 "lako_gemm_tn: M/N/lda/ldb must make 16-byte rows");
-  LAKO_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30), "lako_gemm_tn: dims too large");
-  LAKO_CHECK_ALIGN(A, 16);
-  LAKO_CHECK_ALIGN(B, 16);
-  LAKO_CHECK_ALIGN(C, 4);
-  TnArgs a{};
-  a.n_items = 0;
-  a.A = (const char*)A;
-  a.B = (const char*)B;
-  a.C = C;
-  a.M = (int)M;
-  a.N = (int)N;
-  a.K = (int)K;
-  a.lda = lda;
-  a.ldb = ldb;
-  a.ldc = ldc;
-  a.alpha = alpha;
-  LAKO_CHECK_ARG(rows_out >= 0 && rows_out <= M, "lako_gemm_tn: rows_out");
-  a.Mout = rows_out > 0 ? rows_out : (int)M;
-  a.tiles_m = cdiv(M, TM);
-  a.tiles_n = cdiv(N, TN_);
-  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = tn_check_item("lako_gemm_tn", -1, p, esz)) return rc;
+  const int64_t M = p.M, N = p.N;
+  TnArgs a{};      // (n_items 0: one problem; no slabs)
+  a.A = (const char*)p.a; a.B = (const char*)p.b; a.C = p.c; a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.lda = p.lda; a.ldb = p.ldb; a.ldc = p.ldc; a.alpha = p.alpha;
+  a.Mout = p.rows_out > 0 ? p.rows_out : (int)M;      // rows_out: 0 = M, else only the first rows_out rows of C are written
   if (in_dtype == LAKO_BF16 && M >= 256 && N >= 256 && tu.tn_big) {
     a.tiles_m = cdiv(M, 256);
     a.tiles_n = cdiv(N, 256);
@@ -2672,90 +2735,116 @@ static int tn_single(const void* A, const void* B, float* C, int64_t M, int64_t 
       if (sk > max_split) sk = max_split;
       if (sk < 1) sk = 1;
     }
-    int chunk = cdiv(cdiv(K, sk), 64) * 64;
-    a.split_k = cdiv(K, chunk);
-    a.k_chunk = chunk;
+    a.k_chunk = cdiv(cdiv(K, sk), 64) * 64;
+    a.split_k = cdiv(K, a.k_chunk);
     a.no_atomics = tu.tn_big == 2;
     a.glds = tu.nt_glds;
     a.no_stagger = 1;      // (as the grouped launch: see lako_gemm_tn_grouped)
     a.out_mode = a.split_k == 1 ? out_mode : 0;
-    a.wide_out = reinterpret_cast<uintptr_t>(C) % 16 == 0 && ldc % 4 == 0 && N % 4 == 0;
-    a.slabs = nullptr;
-    a.tickets = nullptr;
-    LAKO_CHECK_ARG((int64_t)64 * lda * 2 < (1ll << 31) && (int64_t)64 * ldb * 2 < (1ll << 31),
-                   "lako_gemm_tn: leading dimension too large");
-    if (tn4_ok(a, tu)) {
-      LAKO_SET_MAX_LDS((&gemm_tn4_kernel), tn4::LDS_BYTES);
-      hipLaunchKernelGGL(gemm_tn4_kernel, dim3(tiles * a.split_k), dim3(256), tn4::LDS_BYTES, s, a);
-    } else if (a.glds && a.k_chunk % 64 == 0) {
-      LAKO_SET_MAX_LDS((&gemm_tn256_kernel<true>), 4 * TN2_IMG);
-      hipLaunchKernelGGL(gemm_tn256_kernel<true>, dim3(tiles * a.split_k), dim3(512), 4 * TN2_IMG, s, a);
-    } else {
-      LAKO_SET_MAX_LDS((&gemm_tn256_kernel<false>), 4 * TN2_IMG);
-      hipLaunchKernelGGL(gemm_tn256_kernel<false>, dim3(tiles * a.split_k), dim3(512), 4 * TN2_IMG, s, a);
-    }
+    a.wide_out = reinterpret_cast<uintptr_t>(p.c) % 16 == 0 && p.ldc % 4 == 0 && N % 4 == 0;
+    launch_tn256(a, tu, tiles * a.split_k, s);
     LAKO_LAUNCH_CHECK();
     return LAKO_OK;
   }
+  a.tiles_m = cdiv(M, TM);
+  a.tiles_n = cdiv(N, TN_);
   if (out_mode == 2) {      // the small-tile kernel only adds: overwrite = zero, then add
-    if (hipMemset2DAsync(C, (size_t)ldc * 4, 0, (size_t)N * 4, (size_t)a.Mout, (hipStream_t)stream) != hipSuccess) {
+    if (hipMemset2DAsync(p.c, (size_t)p.ldc * 4, 0, (size_t)N * 4, (size_t)a.Mout, s) != hipSuccess) {
       lako_set_error("lako_gemm_tn: could not zero the output");
       return LAKO_E_LAUNCH;
     }
   }
   const int kr = in_dtype == LAKO_BF16 ? 64 : 32;
   if (split_k <= 0) {  // auto: aim at >= 2 workgroups per CU, at least 4 K-steps per split
-    int tiles = a.tiles_m * a.tiles_n;
-    split_k = cdiv(512, tiles);
-    int max_split = cdiv(K, (int64_t)kr * 4);
+    split_k = cdiv(512, a.tiles_m * a.tiles_n);
+    const int max_split = cdiv(K, (int64_t)kr * 4);
     if (split_k > max_split) split_k = max_split;
     if (split_k < 1) split_k = 1;
   }
-  int chunk = cdiv(K, split_k);
-  chunk = cdiv(chunk, kr) * kr;
-  a.split_k = cdiv(K, chunk);
-  a.k_chunk = chunk;
-  // voffset (row * ld_bytes) must stay below 2^32 within one K-step: rows < 64
-  LAKO_CHECK_ARG((int64_t)64 * lda * esz < (1ll << 31) && (int64_t)64 * ldb * esz < (1ll << 31),
-                 "lako_gemm_tn: leading dimension too large");
+  a.k_chunk = cdiv(cdiv(K, split_k), kr) * kr;
+  a.split_k = cdiv(K, a.k_chunk);
   if (in_dtype == LAKO_BF16) launch_tn<bf16_t>(a, s);
   else launch_tn<float>(a, s);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }
 
-// K-splits the grouped launch would use (the same arithmetic as the launch itself)
-static int tn_grouped_plan(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int split_k, const lako_tuning_t& tu, int* tiles_out) {
-  int tiles = 0;
-  for (int i = 0; i < n_items; ++i) tiles += cdiv((int)items[i].M, 256) * cdiv((int)items[i].N, 256);
+extern "C" int lako_gemm_tn(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda,
+                            int64_t ldb, int64_t ldc, int in_dtype, float alpha, int split_k, const lako_tuning_t* tuning,
+                            lako_stream_t stream) {
+  const lako_gemm_tn_item_t p = {A, B, C, M, N, lda, ldb, ldc, alpha, 0};
+  return tn_single(p, K, in_dtype, split_k, tuning ? *tuning : process_tuning(), (hipStream_t)stream);
+}
+
+// ---- the grouped TN plan: how one launch of the 256² weight-gradient kernels cuts K.  Reads its arguments (and LAKO_DETERMINISTIC) and
+// nothing else; lako_gemm_tn_grouped_workspace sizes the scratch from it and lako_gemm_tn_grouped launches by it ---------------------------
+struct TnGroupedPlan {
+  int tiles;                         // 256² output tiles of all items
+  int split_k, k_chunk;              // K-pieces per tile (the tiles after t_full) and their rows (a multiple of 64)
+  int t_full;                        // HYBRID: the first t_full tiles run their whole K in one workgroup each; 0 = uniform splits
+  bool slabs;                        // the K-splits may meet through partial tiles in a caller's workspace instead of atomics …
+  int64_t slab_bytes, tick_bytes;    // … of slab_bytes + tick_bytes: the partial tiles, then one arrival counter per tile (256-byte granules)
+};
+
+// the shapes the grouped launch takes (all others: one lako_gemm_tn launch per item, no workspace)
+static bool tn_grouped_is_big(const lako_gemm_tn_item_t* items, int n_items, int in_dtype, const lako_tuning_t& tu) {
+  bool big = in_dtype == LAKO_BF16 && tu.tn_big;
+  for (int i = 0; i < n_items; ++i) big = big && items[i].M >= 256 && items[i].N >= 256;
+  return big;
+}
+
+static TnGroupedPlan tn_grouped_plan(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int split_k, const lako_tuning_t& tu) {
+  TnGroupedPlan pl{};
+  for (int i = 0; i < n_items; ++i) pl.tiles += cdiv((int)items[i].M, 256) * cdiv((int)items[i].N, 256);
+  // LAKO_DETERMINISTIC=1: no hybrid schedule (its short units meet by float atomics); the uniform splits go through the
+  // workspace slabs, summed in split order — and without a workspace one contributor per element (lako_gemm_tn_grouped)
+  if (lako_det::on() && split_k == -3) split_k = 0;
   const int max_split = cdiv(K, 64 * 4);
-  if (lako_det::on() && split_k == -3) split_k = 0;      // (as the launch)
-  int sk = tn_pick_split(tiles, K, max_split);
-  if (tu.tn_split > 0) sk = tu.tn_split;
-  if (split_k > 0) sk = split_k;
-  if (split_k < 0) sk = 1;
+  int sk = tn_pick_split(pl.tiles, K, max_split);      // the library's choice (split_k 0, and a hybrid launch of less than one round)
+  if (split_k == -3) {
+    // HYBRID (round 4): ⌊tiles / 256⌋ whole rounds of full-K tiles (one contributor: plain adds, no atomic pass, a third of the
+    // prologues) + the remaining tiles cut finely enough to fill one or a few short rounds.  Uniform splits pay a last round of full-length
+    // units on a fraction of the chip (1 296 tiles × 3 = 15.19 rounds → 16) and one atomic pass of 256 KiB per unit — ≈ 50 µs of a 450 µs
+    // unit at the chip's ≈ 1.3 TB/s, during which the CU's only workgroup does nothing else.
+    const int full = (pl.tiles / 256) * 256, rem = pl.tiles - full;
+    if (full > 0) {
+      double best_cost = 1e30;
+      for (int c = 1; c <= 16 && c <= max_split; ++c) {      // remainder phase in full-unit times: rounds of 1/c-length units
+        const double cost = rem ? (double)cdiv((int64_t)rem * c, 256) / c + 0.004 * c : 0.0;
+        if (cost < best_cost - 1e-9) { best_cost = cost; sk = c; }
+      }
+      pl.t_full = full;
+    }
+  } else if (split_k != 0) {
+    sk = split_k < 0 ? 1 : split_k;      // (−1 / −2: one contributor)
+  } else if (tu.tn_split > 0) {
+    sk = tu.tn_split;
+  }
   if (sk > max_split) sk = max_split;
   if (sk < 1) sk = 1;
-  const int chunk = cdiv(cdiv(K, sk), 64) * 64;
-  *tiles_out = tiles;
-  return cdiv(K, chunk);
+  pl.k_chunk = cdiv(cdiv(K, sk), 64) * 64;
+  pl.split_k = cdiv(K, pl.k_chunk);
+  // the pieces of a hybrid launch add by atomics (include/lako_hip.h): it never asks for a workspace
+  pl.slabs = pl.split_k > 1 && split_k != -3;
+  if (pl.slabs) {
+    pl.slab_bytes = (int64_t)pl.tiles * pl.split_k * 65536 * 4;
+    pl.tick_bytes = (int64_t)((pl.tiles + 63) / 64) * 256;
+  }
+  return pl;
 }
 
 extern "C" int64_t lako_gemm_tn_grouped_workspace(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k,
                                                   const lako_tuning_t* tuning) {
   const lako_tuning_t& tu = tuning ? *tuning : process_tuning();
-  if (!items || n_items < 1 || n_items > LAKO_TN_GROUP_MAX || K <= 0 || in_dtype != LAKO_BF16 || !tu.tn_big) return 0;
-  for (int i = 0; i < n_items; ++i)
-    if (items[i].M < 256 || items[i].N < 256) return 0;
-  int tiles = 0;
-  const int sk = tn_grouped_plan(items, n_items, K, split_k, tu, &tiles);
-  if (sk <= 1) return 0;
-  return (int64_t)tiles * sk * 65536 * 4 + (int64_t)((tiles + 63) / 64) * 256;      // slabs + tickets (256-byte granules)
+  if (!items || n_items < 1 || n_items > LAKO_TN_GROUP_MAX || K <= 0 || !tn_grouped_is_big(items, n_items, in_dtype, tu)) return 0;
+  const TnGroupedPlan pl = tn_grouped_plan(items, n_items, K, split_k, tu);
+  return pl.slab_bytes + pl.tick_bytes;
 }
 
 extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k,
                                     const lako_tuning_t* tuning, void* workspace, int64_t workspace_bytes, lako_stream_t stream) {
   const lako_tuning_t& tu = tuning ? *tuning : process_tuning();
+  hipStream_t s = (hipStream_t)stream;
   LAKO_CHECK_ARG(items && n_items >= 1 && n_items <= LAKO_TN_GROUP_MAX, "lako_gemm_tn_grouped: 1..%d items", LAKO_TN_GROUP_MAX);
   LAKO_CHECK_ARG(split_k >= -3, "lako_gemm_tn_grouped: split_k %d", split_k);
   LAKO_CHECK_ARG(K > 0 && K < (1 << 30), "lako_gemm_tn_grouped: bad K");
@@ -2782,16 +2871,9 @@ extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_item
       }
     }
   }
-  // LAKO_DETERMINISTIC=1: no hybrid schedule (its short units meet by float atomics); the uniform splits below go through the
-  // workspace slabs, summed in split order — and without a workspace one contributor per element
-  const bool det = lako_det::on();
-  if (det && split_k == -3) split_k = 0;
-  bool big = in_dtype == LAKO_BF16 && tu.tn_big;
-  for (int i = 0; i < n_items; ++i) big = big && items[i].M >= 256 && items[i].N >= 256;
-  if (!big) {   // shapes the 256×256 kernel does not take: one launch per problem
+  if (!tn_grouped_is_big(items, n_items, in_dtype, tu)) {   // shapes the 256×256 kernel does not take: one launch per problem
     for (int i = 0; i < n_items; ++i) {
-      int rc = tn_single(items[i].a, items[i].b, items[i].c, items[i].M, items[i].N, K, items[i].lda, items[i].ldb,
-                         items[i].ldc, in_dtype, items[i].alpha, split_k == -3 ? 0 : split_k, tuning, stream, items[i].rows_out);
+      const int rc = tn_single(items[i], K, in_dtype, split_k == -3 ? 0 : split_k, tu, s);
       if (rc != LAKO_OK) return rc;
     }
     return LAKO_OK;
@@ -2801,25 +2883,19 @@ extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_item
   a.K = (int)K;
   a.no_atomics = tu.tn_big == 2;
   a.glds = tu.nt_glds;
+  a.wide_out = 1;
   int tiles = 0;
   for (int i = 0; i < n_items; ++i) {
     const lako_gemm_tn_item_t& p = items[i];
-    LAKO_CHECK_ARG(p.a && p.b && p.c && p.M > 0 && p.N > 0, "lako_gemm_tn_grouped: item %d: null operand / empty problem", i);
-    LAKO_CHECK_ARG((p.M * 2) % 16 == 0 && (p.N * 2) % 16 == 0 && (p.lda * 2) % 16 == 0 && (p.ldb * 2) % 16 == 0,
-                   "lako_gemm_tn_grouped: item %d: M/N/lda/ldb must make 16-byte rows", i);
-    LAKO_CHECK_ARG(p.M < (1 << 30) && p.N < (1 << 30) && (int64_t)64 * p.lda * 2 < (1ll << 31) && (int64_t)64 * p.ldb * 2 < (1ll << 31),
-                   "lako_gemm_tn_grouped: item %d: dims too large", i);
-    LAKO_CHECK_ALIGN(p.a, 16);
-    LAKO_CHECK_ALIGN(p.b, 16);
-    LAKO_CHECK_ALIGN(p.c, 4);
+    if (const int rc = tn_check_item("lako_gemm_tn_grouped", i, p, 2)) return rc;
     TnArgs::Item& d = a.items[i];
     d.A = (const char*)p.a; d.B = (const char*)p.b; d.C = p.c; d.M = (int)p.M; d.N = (int)p.N;
     d.lda = p.lda; d.ldb = p.ldb; d.ldc = p.ldc; d.alpha = p.alpha;
-    LAKO_CHECK_ARG(p.rows_out >= 0 && p.rows_out <= p.M, "lako_gemm_tn_grouped: item %d: rows_out", i);
     d.Mout = p.rows_out > 0 ? p.rows_out : (int)p.M;
     d.tiles_n = cdiv((int)p.N, 256);
     d.tile_start = tiles;
     tiles += cdiv((int)p.M, 256) * d.tiles_n;
+    if (reinterpret_cast<uintptr_t>(p.c) % 16 != 0 || p.ldc % 4 != 0 || p.N % 4 != 0) a.wide_out = 0;
   }
   // every wave issues its DMA at the top of the K-step (round 4, with the full-K units: 7.29 -> 7.04 ms per step against waves 4-7 issuing
   // theirs two MFMA rows later, the NT kernel's order; LAKO_TN_STAGGER=1 restores that)
@@ -2827,69 +2903,26 @@ extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_item
   a.no_stagger = !tn_stag;
   a.tiles_m = tiles;     // the kernel only uses the product
   a.tiles_n = 1;
-  a.wide_out = 1;
-  for (int i = 0; i < n_items; ++i)
-    if (reinterpret_cast<uintptr_t>(items[i].c) % 16 != 0 || items[i].ldc % 4 != 0 || items[i].N % 4 != 0) a.wide_out = 0;
-  const int max_split = cdiv(K, 64 * 4);
-  int sk = tn_pick_split(tiles, K, max_split);
-  if (tu.tn_split > 0) sk = tu.tn_split;
-  if (split_k > 0) sk = split_k;
-  if (split_k == -1 || split_k == -2) sk = 1;
-  // HYBRID (split_k −3, round 4): ⌊tiles / 256⌋ whole rounds of full-K tiles (one contributor: plain adds, no atomic pass, a third of the
-  // prologues) + the remaining tiles cut finely enough to fill one or a few short rounds.  Uniform splits pay a last round of full-length
-  // units on a fraction of the chip (1 296 tiles × 3 = 15.19 rounds → 16) and one atomic pass of 256 KiB per unit — ≈ 50 µs of a 450 µs
-  // unit at the chip's ≈ 1.3 TB/s, during which the CU's only workgroup does nothing else.
-  a.t_full = 0;
-  if (split_k == -3) {
-    const int full = (tiles / 256) * 256, rem = tiles - full;
-    if (full > 0) {
-      int best = 1;
-      double best_cost = 1e30;
-      for (int c = 1; c <= 16 && c <= max_split; ++c) {      // remainder phase in full-unit times: rounds of 1/c-length units
-        const double cost = rem ? (double)cdiv((int64_t)rem * c, 256) / c + 0.004 * c : 0.0;
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = c; }
-      }
-      a.t_full = full;
-      sk = best;
-    } else {
-      sk = tn_pick_split(tiles, K, max_split);
-    }
-  }
-  if (sk > max_split) sk = max_split;
-  if (sk < 1) sk = 1;
-  const int chunk = cdiv(cdiv(K, sk), 64) * 64;
-  a.split_k = cdiv(K, chunk);
-  a.k_chunk = chunk;
+  const TnGroupedPlan pl = tn_grouped_plan(items, n_items, K, split_k, tu);
+  a.t_full = pl.t_full;
+  a.split_k = pl.split_k;
+  a.k_chunk = pl.k_chunk;
   a.out_mode = ((split_k == -1 || split_k == -2) && a.split_k == 1) ? -split_k : 0;
-  a.slabs = nullptr;
-  a.tickets = nullptr;
-  if (a.split_k > 1 && workspace != nullptr && a.t_full == 0) {      // K-splits meet through partial tiles in the caller's workspace instead of atomics
-    const int64_t slab_bytes = (int64_t)tiles * a.split_k * 65536 * 4, tick_bytes = (int64_t)((tiles + 63) / 64) * 256;
-    if (workspace_bytes >= slab_bytes + tick_bytes && reinterpret_cast<uintptr_t>(workspace) % 16 == 0) {
-      a.slabs = reinterpret_cast<float*>(workspace);
-      a.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + slab_bytes);
-      if (hipMemsetAsync(a.tickets, 0, (size_t)tick_bytes, (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        a.slabs = nullptr;
-        a.tickets = nullptr;
-      }
+  if (pl.slabs && workspace != nullptr && workspace_bytes >= pl.slab_bytes + pl.tick_bytes && reinterpret_cast<uintptr_t>(workspace) % 16 == 0) {
+    a.slabs = reinterpret_cast<float*>(workspace);
+    a.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + pl.slab_bytes);
+    if (hipMemsetAsync(a.tickets, 0, (size_t)pl.tick_bytes, s) != hipSuccess) {
+      (void)hipGetLastError();
+      a.slabs = nullptr;
+      a.tickets = nullptr;
     }
   }
-  if (det && a.split_k > 1 && a.slabs == nullptr) {
+  if (lako_det::on() && a.split_k > 1 && a.slabs == nullptr) {      // (no workspace: one contributor per element)
     a.split_k = 1;
     a.k_chunk = cdiv(K, 64) * 64;
   }
   const int grid = a.t_full > 0 ? 8 * (a.t_full / 8 + cdiv((int64_t)(tiles - a.t_full) * a.split_k, 8)) : tiles * a.split_k;
-  if (tn4_ok(a, tu)) {
-    LAKO_SET_MAX_LDS((&gemm_tn4_kernel), tn4::LDS_BYTES);
-    hipLaunchKernelGGL(gemm_tn4_kernel, dim3(grid), dim3(256), tn4::LDS_BYTES, (hipStream_t)stream, a);
-  } else if (a.glds && a.k_chunk % 64 == 0) {
-    LAKO_SET_MAX_LDS((&gemm_tn256_kernel<true>), 4 * TN2_IMG);
-    hipLaunchKernelGGL(gemm_tn256_kernel<true>, dim3(grid), dim3(512), 4 * TN2_IMG, (hipStream_t)stream, a);
-  } else {
-    LAKO_SET_MAX_LDS((&gemm_tn256_kernel<false>), 4 * TN2_IMG);
-    hipLaunchKernelGGL(gemm_tn256_kernel<false>, dim3(grid), dim3(512), 4 * TN2_IMG, (hipStream_t)stream, a);
-  }
+  launch_tn256(a, tu, grid, s);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }
@@ -2924,75 +2957,39 @@ extern "C" int lako_gemm_nt_mx(const lako_gemm_nt_t* p, const uint8_t* a_scales,
   LAKO_CHECK_ALIGN(b_scales, 4);
   if (p->flags & LAKO_EPI_RESID) LAKO_CHECK_ARG(p->resid != nullptr && p->ldr % 4 == 0, "lako_gemm_nt_mx: RESID needs resid, ldr %% 4 == 0");
   if (p->flags & LAKO_EPI_AUXMASK) LAKO_CHECK_ARG(p->aux != nullptr && p->ldaux % 4 == 0, "lako_gemm_nt_mx: AUXMASK needs aux (bf16), ldaux %% 4 == 0");
+  hipStream_t s = (hipStream_t)stream;
+  const lako_tuning_t& tu = p->tuning ? *p->tuning : process_tuning();
   MxArgs m;
   NtArgs& a = m.nt;
-  a = NtArgs{};
-  a.A = (const char*)p->A;
-  a.B = (const char*)p->B;
-  a.C = (char*)p->C;
-  a.resid = (const char*)p->resid;
-  a.aux = (const char*)p->aux;
-  a.M = (int)p->M;
-  a.N = (int)p->N;
-  a.K = (int)p->K;
-  a.lda = p->lda;
-  a.ldb = p->ldb;
-  a.ldc = p->ldc;
-  a.ldr = p->ldr;
-  a.ldaux = p->ldaux;
-  a.alpha = p->alpha;
-  a.aux_scale = p->aux_scale;
-  a.flags = p->flags;
-  a.drop_thresh = p->drop.p > 0.f ? lako_drop_thresh(p->drop.p) : 0u;
-  a.drop_scale = p->drop.p > 0.f ? 1.0f / (1.0f - p->drop.p) : 1.0f;
-  a.drop_key = lako_drop_key(p->drop.seed, p->drop.site);
+  a = nt_args_from(p);
   a.tiles_m = cdiv(a.M, 256);
   a.tiles_n = cdiv(a.N, 256);
-  const lako_tuning_t& tu = p->tuning ? *p->tuning : process_tuning();
-  a.group_m = a.tiles_n >= 16 ? (tu.nt_group_m < 0 ? -tu.nt_group_m : tu.nt_group_m) : (tu.nt_group_m < 0 ? -tu.nt_group_m : 0);
   a.wide_epi = !(a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK));
   m.sa = a_scales;
   m.sb = b_scales;
   m.ksp = (int)(((p->K / 128) + 3) / 4 * 4);
   // round 6: the four-wave tile with two K-slices in flight (gemm_nt4_mx.h) where it applies — whole groups of four K-steps, at least one
-  // round of the chip, the epilogues nt4_epilogue has (nt4_ok's rules), 32-bit offsets; the tile height by the rounds of the chip as for bf16
-  {
-    const int side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
-    bool ok = tu.nt_four && a.K % 512 == 0 && (int64_t)cdiv(a.M, 256) * cdiv(a.N, 256) >= 256 && (int64_t)256 * std::max(a.lda, a.ldb) < (1ll << 31) &&
-              (int64_t)128 * a.ldc * 2 < (1ll << 31) && !(a.alpha != 1.0f && (a.flags != 0 || a.drop_thresh != 0)) &&
-              !(a.drop_thresh != 0 && (uint64_t)(a.M + 256) * (uint64_t)a.N >= (1ull << 34)) && side != (LAKO_EPI_RESID | LAKO_EPI_AUXMASK) &&
-              !(side && (a.flags & LAKO_EPI_RELU)) && !(side == LAKO_EPI_AUXMASK && a.drop_thresh != 0);
-    if (side == LAKO_EPI_RESID) ok = ok && a.ldr % 8 == 0 && reinterpret_cast<uintptr_t>(a.resid) % 16 == 0 && (int64_t)128 * a.ldr * 2 < (1ll << 31);
-    if (side == LAKO_EPI_AUXMASK) ok = ok && a.ldaux % 8 == 0 && reinterpret_cast<uintptr_t>(a.aux) % 16 == 0 && (int64_t)128 * a.ldaux * 2 < (1ll << 31);
-    if (ok) {
-      const int nkx = a.K / 128, tn = cdiv(a.N, 256);
-      const double c8 = (double)cdiv((int64_t)cdiv(a.M, 256) * tn, 256) * (4.5 + 1.6 * nkx);
-      const double c6 = (double)cdiv((int64_t)cdiv(a.M, 192) * tn, 256) * (4.5 + 1.25 * nkx);
-      const bool six = tu.nt_variant == 3 || (tu.nt_variant != 9 && c6 < c8);
-      a.tiles_m = cdiv(a.M, six ? 192 : 256);
-      a.group_m = tu.nt_group_m < 0 ? -tu.nt_group_m : (a.tiles_n >= 8 ? tu.nt_group_m : 0);
-      a.dephase = 0;
-      a.epi_direct = 0;
-      int g4 = a.tiles_m * a.tiles_n;
-      if (g4 > 256) g4 = 256;
-#define LAKO_MX4(MT_, SIDE_)                                                                                         \
-  do {                                                                                                               \
-    LAKO_SET_MAX_LDS((&gemm_nt4_mx_kernel<MT_, SIDE_>), nt4::LDS_BYTES);                                             \
-    hipLaunchKernelGGL((gemm_nt4_mx_kernel<MT_, SIDE_>), dim3(g4), dim3(256), nt4::LDS_BYTES, (hipStream_t)stream, m); \
-  } while (0)
-      if (six) { if (side) LAKO_MX4(6, true); else LAKO_MX4(6, false); }
-      else { if (side) LAKO_MX4(8, true); else LAKO_MX4(8, false); }
-#undef LAKO_MX4
-      LAKO_LAUNCH_CHECK();
-      return LAKO_OK;
-    }
+  // round of the chip, the epilogues and 32-bit offsets of nt4_epilogue_ok (the ticket queue does not concern this kernel: nt_queue is not
+  // consulted); the tile height by the rounds of the chip as for bf16, or forced by variants 3 / 9
+  if (tu.nt_four && a.K % 512 == 0 && (int64_t)a.tiles_m * a.tiles_n >= 256 && nt4_epilogue_ok(a, 1)) {
+    const bool six = tu.nt_variant == 3 || (tu.nt_variant != 9 && nt4_prefers_192(a.M, a.N, a.K / 128, 1.6, 1.25));
+    const bool side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
+    a.tiles_m = cdiv(a.M, six ? 192 : 256);
+    a.group_m = nt_group_m(tu, a.tiles_n);
+    a.dephase = 0;
+    a.epi_direct = 0;
+    if (six) side ? launch_nt4_mx_kernel<6, true>(m, s) : launch_nt4_mx_kernel<6, false>(m, s);
+    else side ? launch_nt4_mx_kernel<8, true>(m, s) : launch_nt4_mx_kernel<8, false>(m, s);
+    LAKO_LAUNCH_CHECK();
+    return LAKO_OK;
   }
-  int grid = a.tiles_m * a.tiles_n;
-  if (grid > 256) grid = 256;
-  a.dephase = (tu.nt_dephase > 0 && a.tiles_m * a.tiles_n > grid) ? ((tu.nt_dephase_n << 16) | (tu.nt_dephase & 0xffff)) : 0;
+  // the eight-wave kernel bands from 16 tile columns on
+  a.group_m = nt_group_m(tu, a.tiles_n, 16);
+  const int grid = std::min(a.tiles_m * a.tiles_n, 256);
+  a.dephase = a.tiles_m * a.tiles_n > grid ? nt_dephase_word(tu) : 0;
   constexpr int LDS = 2 * (256 + 256) * TKB;
   LAKO_SET_MAX_LDS((&gemm_nt_mx_kernel), LDS);
-  hipLaunchKernelGGL(gemm_nt_mx_kernel, dim3(grid), dim3(512), LDS, (hipStream_t)stream, m);
+  hipLaunchKernelGGL(gemm_nt_mx_kernel, dim3(grid), dim3(512), LDS, s, m);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }
