@@ -84,10 +84,14 @@ typedef struct lako_tuning {
                             counted waits, waves 4-7 one barrier behind waves 0-3.  Same results bit for bit */
   int32_t nt_glds;       /* 1 (default): whole K-slices are staged by global_load_lds (rows past the edge clamped) instead of
                             buffer_load ... lds; partial K-slices (K % 64) keep the buffer form and its zero fill */
-  int32_t nt_tile288;    /* 1 (default): 288-row tiles (variant 8) where they save a round or the tail launch — plain epilogues only */
-  int32_t nt_four;       /* 1 (default, round 6): problems of at least one round of 256x256 tiles with bf16 operands and output, K % 128 == 0 and
-                            one of the epilogues {alpha, ReLU, dropout} / {residual, dropout} / {aux mask} run on the four-wave kernels with
+  int32_t nt_tile288;    /* 1 (default): 288-row tiles (variant 8) where they save a round or the tail launch — bf16 in and out, every epilogue
+                            but the atomic one (a side operand in 16-row passes), static tile order: not under nt_queue */
+  int32_t nt_four;       /* 1 (default, round 6): problems of at least one round of 256x256 tiles with bf16 operands and output, K % 128 == 0, K >= 256 and
+                            one of the epilogues alpha alone / {ReLU, dropout} / {residual, dropout} / {aux mask} — every one but the first with
+                            alpha = 1, no ReLU next to a residual or aux operand, no dropout next to the aux mask; N % 8 == 0, ldc % 8 == 0,
+                            C and the side operand 16-byte aligned with ldr / ldaux % 8 == 0 — run on the four-wave kernels with
                             the hand-placed K loop (256- or 192-row tiles, whichever needs less time for the launch's rounds of the chip);
+                            every other call runs as with 0 (lako_gemm_nt_plan tells which);
                             0: the eight-wave kernels of rounds 1-5.  nt_variant 9 / 3 force the 256- / 192-row four-wave kernel.  Same
                             results bit for bit.  3 (= 1 | 2): as 1, but the dropout epilogues without a side operand go through the LDS
                             transposition like the others instead of leaving straight from the accumulator layout (A/B measurements).
@@ -200,6 +204,63 @@ int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_items, int64_t 
  * finish in.  The scratch may be reused by the next launch on the same stream; it holds nothing between launches. */
 int64_t lako_gemm_tn_grouped_workspace(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k,
                                        const lako_tuning_t* tuning);
+
+/* ---- plan queries: WHICH kernel a GEMM call would run, without running it -------------------------------------------------------
+ * Each query takes the arguments of its launching entry point, goes through the same validation and the same decision code (the
+ * launching call consumes the very plan the query reports) and makes no HIP call of any kind: it runs on a host without a GPU, and
+ * no pointer is dereferenced except the host structs.  It returns what the launching call would return before its first launch
+ * (LAKO_E_BADARG / _ALIGN / _UNSUPPORTED agree by construction; `out` is then zeroed) and fills `out` on LAKO_OK.  For tests that pin a kernel and
+ * for callers that want to know which side of a dispatch gate a shape falls on. */
+enum {
+  LAKO_NT_REFUSED = 0,       /* no kernel takes the call */
+  LAKO_NT_FOUR = 1,          /* four-wave 256-column tile with the hand-placed K loop, tile_rows 192 | 256 (tuning nt_four) */
+  LAKO_NT_EIGHT = 2,         /* eight-wave 256-column tile, tile_rows 192 | 256 | 288 (variants 7 / 2 / 8) */
+  LAKO_NT_EIGHT_256x128 = 3, /* eight-wave 256 x 128 tile (variant 1) */
+  LAKO_NT_FOUR_BY_128 = 4,   /* 256 x 256 on four waves of 128 x 128, hipcc's schedule (variant 6, bf16 operands) */
+  LAKO_NT_128 = 5,           /* 128 x 128 tile on four waves (variant 0) */
+  LAKO_NT_RING = 6,          /* 128 x 128 4-slot ring (variant 4; few-tile problems) */
+  LAKO_NT_SKINNY = 7,        /* M <= 256 kernel, K split over the waves; tile_rows = tile side 16 | 32 | 64 (variant 5) */
+  LAKO_NT_SKINNY_NORM = 8,   /* ... with LAKO_EPI_NORM_A */
+  LAKO_NT_FOUR_GATED = 9,    /* four-wave 256-row tile with the fused gated-GELU epilogues (LAKO_EPI_GATED / _BWD) */
+  LAKO_NT_MX_FOUR = 10,      /* lako_gemm_nt_mx: four-wave MX kernel, tile_rows 192 | 256 */
+  LAKO_NT_MX_EIGHT = 11      /* lako_gemm_nt_mx: eight-wave MX kernel */
+};
+typedef struct {
+  int32_t kernel;    /* LAKO_NT_*: the kernel of rows [head_rows, M) — all rows unless there is a tail split */
+  int32_t tile_rows; /* its tile height (LAKO_NT_SKINNY*: the side of its square tile) */
+  int64_t head_rows; /* > 0 (tail split): rows [0, head_rows) run first on LAKO_NT_EIGHT with head_tile-row tiles; a multiple of head_tile */
+  int32_t head_tile;
+  /* decisions that select the device code of `kernel` (0 where they do not concern it) ... */
+  int32_t side_lds;     /* LAKO_NT_EIGHT: the residual / aux operand staged through LDS (else read from global memory in the accumulator layout) */
+  int32_t wide_epi;     /* LAKO_NT_EIGHT, LAKO_NT_MX_EIGHT: LDS-transposed epilogue with 16-byte stores (else stores from the accumulator layout) */
+  int32_t queue;        /* LAKO_NT_EIGHT: tiles from the per-XCD ticket counters (the launch still falls back to the static order when the
+                           counters cannot be allocated: first use on a stream that is being captured) */
+  int32_t eight_phase;  /* LAKO_NT_EIGHT: the 8-phase main loop (tuning nt_pp) */
+  int32_t skinny_steps; /* LAKO_NT_SKINNY*: K-steps of 32 a wave unrolls: 4 | 8 | 16 */
+  /* ... and the same for the head launch of a tail split */
+  int32_t head_side_lds, head_wide_epi, head_queue, head_eight_phase;
+} lako_gemm_plan_t;
+int lako_gemm_nt_plan(const lako_gemm_nt_t* p, lako_gemm_plan_t* out);
+int lako_gemm_nt_mx_plan(const lako_gemm_nt_t* p, const uint8_t* a_scales, const uint8_t* b_scales, lako_gemm_plan_t* out);
+
+typedef struct {
+  int32_t per_item;   /* lako_gemm_tn_grouped only: 1 = shapes the grouped 256 x 256 launch does not take, one lako_gemm_tn launch per item
+                         (the fields below then describe item 0's launch) */
+  int32_t big;        /* 1: the 256 x 256 weight-gradient kernel; 0: the 128 x 128 kernel (fp32 operands, M or N < 256, tuning tn_big 0) */
+  int32_t four;       /* 1: the four-wave 256 x 256 kernel (tuning tn_four) */
+  int32_t tiles;      /* output tiles of all items */
+  int32_t split_k;    /* K-pieces per tile (hybrid: of the tiles after full_tiles) */
+  int32_t k_chunk;    /* rows of K per piece */
+  int32_t full_tiles; /* hybrid schedule (split_k -3): the first full_tiles tiles run their whole K in one workgroup each; 0 = uniform pieces */
+  int32_t slabs;      /* 1: the pieces meet through partial tiles in the caller's workspace, summed in piece order */
+  int32_t atomics;    /* 1: contributions are added to C by fp32 atomics */
+  int32_t out_mode;   /* one piece per tile: 0 adds as `atomics` says, 1 plain read-modify-write (split_k -1), 2 overwrite (split_k -2) */
+  int32_t grid;       /* workgroups of the launch */
+} lako_gemm_tn_plan_t;
+int lako_gemm_tn_plan(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                      int in_dtype, float alpha, int split_k, const lako_tuning_t* tuning, lako_gemm_tn_plan_t* out);
+int lako_gemm_tn_grouped_plan(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k,
+                              const lako_tuning_t* tuning, void* workspace, int64_t workspace_bytes, lako_gemm_tn_plan_t* out);
 
 /* ---- T5LayerNorm (RMSNorm, HF5:59-72): y = dropout(x * rsqrt(mean(x²) + eps) * w) ----------------
  * rstd [rows] fp32 is written for the backward.  w is fp32 [d]. */

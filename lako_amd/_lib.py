@@ -48,6 +48,30 @@ class GemmTNItem(C.Structure):
                 ("alpha", f32), ("rows_out", i32)]
 
 
+class GemmPlan(C.Structure):
+    """lako_gemm_plan_t: what lako_gemm_nt_plan / lako_gemm_nt_mx_plan say the launching call would run"""
+    _fields_ = [("kernel", i32), ("tile_rows", i32), ("head_rows", i64), ("head_tile", i32), ("side_lds", i32), ("wide_epi", i32),
+                ("queue", i32), ("eight_phase", i32), ("skinny_steps", i32), ("head_side_lds", i32), ("head_wide_epi", i32),
+                ("head_queue", i32), ("head_eight_phase", i32)]
+
+    def __repr__(self):
+        return "GemmPlan(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_ if getattr(self, n) or n == "kernel") + ")"
+
+
+# lako_gemm_plan_t.kernel (include/lako_hip.h LAKO_NT_*)
+(NT_REFUSED, NT_FOUR, NT_EIGHT, NT_EIGHT_256x128, NT_FOUR_BY_128, NT_128, NT_RING, NT_SKINNY, NT_SKINNY_NORM, NT_FOUR_GATED, NT_MX_FOUR,
+ NT_MX_EIGHT) = range(12)
+
+
+class GemmTNPlan(C.Structure):
+    """lako_gemm_tn_plan_t (lako_gemm_tn_plan / lako_gemm_tn_grouped_plan)"""
+    _fields_ = [(n, i32) for n in ("per_item", "big", "four", "tiles", "split_k", "k_chunk", "full_tiles", "slabs", "atomics", "out_mode",
+                                   "grid")]
+
+    def __repr__(self):
+        return "GemmTNPlan(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 TN_GROUP_MAX = 48
 HB_MULTI_MAX = 24          # problems per lako_headbatch_tn_multi launch
 
@@ -90,6 +114,11 @@ SIGNATURES = {
     "lako_gemm_tn": [vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, f32, i32, vp, vp],
     "lako_gemm_tn_grouped": [C.POINTER(GemmTNItem), i32, i64, i32, i32, vp, vp, i64, vp],
     "lako_gemm_tn_grouped_workspace": [C.POINTER(GemmTNItem), i32, i64, i32, i32, vp],
+    # plan queries: the decision of the launching entry point without the launch (no HIP call: they run on a host without a GPU)
+    "lako_gemm_nt_plan": [C.POINTER(GemmNT), C.POINTER(GemmPlan)],
+    "lako_gemm_nt_mx_plan": [C.POINTER(GemmNT), vp, vp, C.POINTER(GemmPlan)],
+    "lako_gemm_tn_plan": [vp, vp, vp, i64, i64, i64, i64, i64, i64, i32, f32, i32, vp, C.POINTER(GemmTNPlan)],
+    "lako_gemm_tn_grouped_plan": [C.POINTER(GemmTNItem), i32, i64, i32, i32, vp, vp, i64, C.POINTER(GemmTNPlan)],
     # data-parallel communication (RCCL behind the C-ABI; the Python host itself uses torch.distributed — lako_amd/dist.py) and the
     # workspace query of SURVEY.md §8 b2
     "lako_comm_unique_id": [C.POINTER(C.c_uint8)],

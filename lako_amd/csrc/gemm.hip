@@ -2021,7 +2021,7 @@ const TuneKey TUNE_KEYS[] = {
 
 void tuning_defaults(lako_tuning_t* t) {
   memset(t, 0, sizeof(*t));
-  t->nt_variant = -1;      // -1 auto; 0: 128x128 / 4 waves; 1: 256x128 / 8 waves; 2: 256x256 / 8 waves; 4: 128x128 ring; 5: split-K skinny; 6: 256x256 / 4 waves (experiment); 7: 192x256 / 8 waves; 8: 288x256 / 8 waves (plain epilogues)
+  t->nt_variant = -1;      // -1 auto; 0: 128x128 / 4 waves; 1: 256x128 / 8 waves; 2: 256x256 / 8 waves; 4: 128x128 ring; 5: split-K skinny; 6: 256x256 / 4 waves (experiment); 7: 192x256 / 8 waves; 8: 288x256 / 8 waves (bf16 in and out, every epilogue but the atomic one)
   t->nt_tail_split = 1;
   t->nt_ring = 1;          // skinny problems go to gemm_nt_ring_kernel (0 disables; variant 4 forces it)
   t->nt_skinny = 1;        // M <= 256 rows: gemm_nt_skinny_kernel (0 disables, 2 / 3 / 4 force 64² / 32² / 16² tiles; variant 5 forces the kernel)
@@ -2036,7 +2036,7 @@ void tuning_defaults(lako_tuning_t* t) {
   t->tn_split = 0;         // > 0: force the number of K-splits of the 256x256 TN kernel (A/B measurements)
   t->nt_glds = 1;          // K-slice staging of the 256² kernels by global_load_lds (0: buffer_load … lds everywhere)
   t->nt_pp = 0;            // 1: the 8-phase main loop of the 256² / 8-wave bf16 kernel (measured slower, A/B only); 0: the two-phase loop
-  t->nt_tile288 = 1;       // 1: 288-row tiles where the round count favours them (launch_nt; plain epilogues)
+  t->nt_tile288 = 1;       // 1: 288-row tiles where the round count favours them (nt_plan; bf16 in and out, every epilogue but the atomic one, not under nt_queue)
   t->nt_tile192 = 0;       // 1: 192-row tiles where the round count favours them (launch_nt) — measured no faster, off
   t->nt_four = 1;          // 1: the four-wave kernels with the hand-placed K loop (gemm_nt4.h) wherever they apply
   t->tn_four = 1;          // 1: the same for the 256² weight-gradient kernel (gemm_tn4.h)
@@ -2243,13 +2243,41 @@ NtArgs nt_rows_from(NtArgs a, int64_t r0) {
   return a;
 }
 
-// ---- NT launchers: one kernel family each; they fill in the launch-dependent fields of NtArgs ---------------------------------------
-template <typename T, typename TO, int WM, int WN, int MT, int NT, bool SIDE = false, bool QUEUE = false, bool PP = false>
-void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
+// ---- the decisions the NT launchers used to take on their way to the launch, as pure functions of the arguments: nt_choice makes them
+// part of the plan (lako_gemm_nt_plan reports them), the launchers carry them out ---------------------------------------------------------
+struct NtChoice {
+  int side_lds;       // NT_EIGHT: the SIDE instantiation (residual / aux operand staged through LDS)
+  int wide_epi;       // NT_EIGHT: NtArgs::wide_epi
+  int queue;          // NT_EIGHT, 256-row tiles: the QUEUE instantiation
+  int eight_phase;    // NT_EIGHT, 256-row tiles: the PP instantiation
+  int skinny_steps;   // NT_SKINNY / _NORM: the MAXS instantiation (4 | 8 | 16)
+};
+
+// LDS bytes of a gemm_nt_kernel instantiation
+template <typename T, int WM, int WN, int MT, int NT, bool SIDE>
+constexpr int nt_cfg_lds() {
   constexpr int BM = WM * MT * 16, BN = WN * NT * 16, NW_ = WM * WN, BUF_ = (BM + BN) * TKB;
   // + the epilogue scratch of the waves that do not fit the free K-slice buffer (8 KiB each; 192-row tiles: one wave)
   constexpr int EXTRA = (sizeof(T) == 2 && NW_ == 8 && BUF_ / 8192 < NW_) ? (NW_ - BUF_ / 8192) * 8192 : 0;
-  constexpr int LDS = 2 * BUF_ + (SIDE ? NW_ * (MT % 2 == 0 ? 32 : 16) * 128 : 0) + EXTRA;
+  return 2 * BUF_ + (SIDE ? NW_ * (MT % 2 == 0 ? 32 : 16) * 128 : 0) + EXTRA;
+}
+
+// its grid for `tiles` tiles — persistent: resident workgroups only (LDS-limited: 160 KiB / CU), 256 CUs
+inline int nt_cfg_grid(int tiles, int lds, const lako_tuning_t& tu) {
+  const int per_cu = (160 * 1024) / lds > 0 ? (160 * 1024) / lds : 1;
+  int grid = tiles;
+  if (tu.nt_persistent && grid > 256 * per_cu) grid = 256 * per_cu;
+#ifdef LAKO_EXPERIMENTS
+  if ((tu.nt_debug >> 8) > 0 && grid > (tu.nt_debug >> 8)) grid = tu.nt_debug >> 8;   // timing experiment: fewer resident workgroups
+#endif
+  return grid;
+}
+
+// ---- NT launchers: one kernel family each; they fill in the launch-dependent fields of NtArgs ---------------------------------------
+template <typename T, typename TO, int WM, int WN, int MT, int NT, bool SIDE = false, bool QUEUE = false, bool PP = false>
+void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, const NtChoice& ch, hipStream_t s) {
+  constexpr int BM = WM * MT * 16, BN = WN * NT * 16;
+  constexpr int LDS = nt_cfg_lds<T, WM, WN, MT, NT, SIDE>();
   static_assert(LDS <= 160 * 1024, "LDS");
   LAKO_SET_MAX_LDS((&gemm_nt_kernel<T, TO, WM, WN, MT, NT, SIDE, QUEUE, PP>), LDS);
   a.tiles_m = cdiv(a.M, BM);
@@ -2259,25 +2287,15 @@ void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
   a.store_aux = (int64_t)256 * a.ldc * 2 < (1ll << 31) ? tu.nt_store_aux : 0;   // tile-relative 32-bit store offsets
   a.debug = tu.nt_debug;
   a.group_m = nt_group_m(tu, a.tiles_n);
-  // measured (tools/bench_ops.py --variants 2,32): +6…12 % on plain stores, a LOSS when a residual / aux operand must
-  // be fetched in the row-major layout too — those keep the accumulator-layout epilogue
-  a.wide_epi = tu.nt_wide_epi && !(a.flags & (LAKO_EPI_ATOMIC | LAKO_EPI_RESID | LAKO_EPI_AUXMASK)) && a.N % 8 == 0 &&
-               a.ldc % 8 == 0 && reinterpret_cast<uintptr_t>(a.C) % 16 == 0;
-  // persistent grid: resident workgroups only (LDS-limited: 160 KiB / CU), 256 CUs
-  const int per_cu = (160 * 1024) / LDS > 0 ? (160 * 1024) / LDS : 1;
-  int grid = a.tiles_m * a.tiles_n;
-  if (tu.nt_persistent && grid > 256 * per_cu) grid = 256 * per_cu;
-#ifdef LAKO_EXPERIMENTS
-  if ((tu.nt_debug >> 8) > 0 && grid > (tu.nt_debug >> 8)) grid = tu.nt_debug >> 8;   // timing experiment: fewer resident workgroups
-#endif
+  a.wide_epi = ch.wide_epi;
+  const int grid = nt_cfg_grid(a.tiles_m * a.tiles_n, LDS, tu);
   // DEPHASE: every other workgroup of an XCD starts 1 µs late when the workgroups walk several tiles.  Measured (tools/bench_ops.py
   // --dephase 0,100,…): [64000,768]×[2304,768] 287 → 250 µs, o+res 140 → 134, wi 374 → 366, long launches unchanged; the size of
   // the delay (1…16 µs) and the number of phases (2, 4, 8) do not matter — the lockstep start is what costs.
   a.dephase = a.tiles_m * a.tiles_n > grid ? nt_dephase_word(tu) : 0;
   if constexpr (QUEUE) {
-    a.queue = nt_queue_counters(s);
-    // (several K-steps per tile to cover the ticket's round trip, several tiles per workgroup to be of any use, a persistent grid)
-    if (!a.queue || a.K * (int)sizeof(T) <= TKB || a.tiles_m * a.tiles_n <= grid || !tu.nt_persistent) return launch_nt_cfg<T, TO, WM, WN, MT, NT, SIDE, false>(a, tu, s);
+    a.queue = nt_queue_counters(s);      // (the plan has checked that the queue applies: nt_choice)
+    if (!a.queue) return launch_nt_cfg<T, TO, WM, WN, MT, NT, SIDE, false>(a, tu, ch, s);
   } else {
     a.queue = nullptr;
 #ifdef LAKO_EXPERIMENTS
@@ -2290,27 +2308,21 @@ void launch_nt_cfg(NtArgs a, const lako_tuning_t& tu, hipStream_t s) {
 // the 256-column tile on 8 waves with or without the LDS-staged side operand; 256-row tiles (bf16 in and out) have the ticket-queue and the
 // eight-phase instantiations too
 template <typename T, typename TO, int MT, bool SIDE>
-void launch_nt_256_side(const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
+void launch_nt_256_side(const NtArgs& a, const lako_tuning_t& tu, const NtChoice& ch, hipStream_t s) {
   if constexpr (MT == 8 && sizeof(T) == 2 && sizeof(TO) == 2) {
-    if (tu.nt_queue) return launch_nt_cfg<T, TO, 2, 4, 8, 4, SIDE, true>(a, tu, s);
-    if (nt_pp_mode(tu, a)) return launch_nt_cfg<T, TO, 2, 4, 8, 4, SIDE, false, true>(a, tu, s);
+    if (ch.queue) return launch_nt_cfg<T, TO, 2, 4, 8, 4, SIDE, true>(a, tu, ch, s);
+    if (ch.eight_phase) return launch_nt_cfg<T, TO, 2, 4, 8, 4, SIDE, false, true>(a, tu, ch, s);
   }
-  launch_nt_cfg<T, TO, 2, 4, MT, 4, SIDE>(a, tu, s);
+  launch_nt_cfg<T, TO, 2, 4, MT, 4, SIDE>(a, tu, ch, s);
 }
 
 // the 256² kernel, with the LDS-staged side operand where the epilogue has exactly one (bf16 in and out, 16-B aligned rows)
 template <typename T, typename TO, int MT = 8>
-void launch_nt_256(const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
+void launch_nt_256(const NtArgs& a, const lako_tuning_t& tu, const NtChoice& ch, hipStream_t s) {
   if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {
-    const int side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
-    const char* sp = side == LAKO_EPI_RESID ? a.resid : a.aux;
-    const int64_t ld = side == LAKO_EPI_RESID ? a.ldr : a.ldaux;
-    if (tu.nt_side_lds && (side == LAKO_EPI_RESID || side == LAKO_EPI_AUXMASK) && !(a.flags & LAKO_EPI_ATOMIC) && a.N % 8 == 0 &&
-        a.ldc % 8 == 0 && ld % 8 == 0 && reinterpret_cast<uintptr_t>(a.C) % 16 == 0 && reinterpret_cast<uintptr_t>(sp) % 16 == 0 &&
-        (int64_t)256 * a.ldc * 2 < (1ll << 31) && (int64_t)256 * ld * 2 < (1ll << 31))
-      return launch_nt_256_side<T, TO, MT, true>(a, tu, s);
+    if (ch.side_lds) return launch_nt_256_side<T, TO, MT, true>(a, tu, ch, s);
   }
-  launch_nt_256_side<T, TO, MT, false>(a, tu, s);
+  launch_nt_256_side<T, TO, MT, false>(a, tu, ch, s);
 }
 
 // one four-wave instantiation on a persistent grid of at most one workgroup per CU (a template on the kernel: LAKO_SET_MAX_LDS keeps one
@@ -2389,11 +2401,14 @@ void launch_nt_skinny_steps(const NtArgs& a, hipStream_t s) {
   if constexpr (LDS > 64 * 1024) LAKO_SET_MAX_LDS((&gemm_nt_skinny_kernel<TO, 8, MAXS, TB>), LDS);
   hipLaunchKernelGGL((gemm_nt_skinny_kernel<TO, 8, MAXS, TB>), dim3(cdiv(a.N, TB * 16), cdiv(a.M, TB * 16)), dim3(512), LDS, s, a);
 }
-template <typename TO, int TB>
-void launch_nt_skinny(const NtArgs& a, hipStream_t s) {
+inline int nt_skinny_steps(const NtArgs& a) {
   const int per = cdiv(a.K / 32, 8);
-  if (per <= 4) launch_nt_skinny_steps<TO, 4, TB>(a, s);
-  else if (per <= 8) launch_nt_skinny_steps<TO, 8, TB>(a, s);
+  return per <= 4 ? 4 : per <= 8 ? 8 : 16;
+}
+template <typename TO, int TB>
+void launch_nt_skinny(const NtArgs& a, int steps, hipStream_t s) {
+  if (steps == 4) launch_nt_skinny_steps<TO, 4, TB>(a, s);
+  else if (steps == 8) launch_nt_skinny_steps<TO, 8, TB>(a, s);
   else launch_nt_skinny_steps<TO, 16, TB>(a, s);
 }
 // RMSNorm of A in the fragments: K <= 1024 (all K-steps of a wave resident), 32² tiles
@@ -2432,13 +2447,57 @@ enum NtKernel {
   NT_RING,            // gemm_nt_ring_kernel
   NT_SKINNY,          // gemm_nt_skinny_kernel, `rows` = tile side 16 | 32 | 64
   NT_SKINNY_NORM,     // … with the RMSNorm of A formed in the fragments (LAKO_EPI_NORM_A)
+  NT_FOUR_GATED,      // gemm_nt4_kernel with the fused gated-GELU epilogues (launch_nt4_gated; chosen by nt_decide, not by nt_plan)
+  NT_MX_FOUR,         // gemm_nt4_mx_kernel, `rows` = 192 | 256  (lako_gemm_nt_mx: mx_decide)
+  NT_MX_EIGHT,        // gemm_nt_mx_kernel
 };
+// the public names of lako_gemm_plan_t.kernel are these values
+static_assert(NT_REFUSED == LAKO_NT_REFUSED && NT_FOUR == LAKO_NT_FOUR && NT_EIGHT == LAKO_NT_EIGHT && NT_EIGHT_256x128 == LAKO_NT_EIGHT_256x128 &&
+              NT_FOUR_BY_128 == LAKO_NT_FOUR_BY_128 && NT_128 == LAKO_NT_128 && NT_RING == LAKO_NT_RING && NT_SKINNY == LAKO_NT_SKINNY &&
+              NT_SKINNY_NORM == LAKO_NT_SKINNY_NORM && NT_FOUR_GATED == LAKO_NT_FOUR_GATED && NT_MX_FOUR == LAKO_NT_MX_FOUR &&
+              NT_MX_EIGHT == LAKO_NT_MX_EIGHT, "lako_hip.h LAKO_NT_* mirrors NtKernel");
 struct NtPlan {
   NtKernel kernel;     // runs rows [head_rows, M): all of them unless there is a head
   int rows;
   int64_t head_rows;   // > 0 (TAIL SPLIT): rows [0, head_rows) go to NT_EIGHT with head_tile-row tiles first
   int head_tile;
+  NtChoice main, head; // what the launchers of `kernel` and of the head do with their rows (nt_choice; filled in by nt_plan_full)
 };
+
+// the launcher-level decisions for `kernel` with `rows`-row tiles on the rows of `a`
+template <typename T, typename TO>
+NtChoice nt_choice(NtKernel kernel, int rows, const NtArgs& a, const lako_tuning_t& tu) {
+  NtChoice c{};
+  if (kernel == NT_EIGHT) {
+    if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {
+      // the LDS-staged side operand where the epilogue has exactly one (bf16 in and out, 16-B aligned rows)
+      const int side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
+      const char* sp = side == LAKO_EPI_RESID ? a.resid : a.aux;
+      const int64_t ld = side == LAKO_EPI_RESID ? a.ldr : a.ldaux;
+      c.side_lds = tu.nt_side_lds && (side == LAKO_EPI_RESID || side == LAKO_EPI_AUXMASK) && !(a.flags & LAKO_EPI_ATOMIC) && a.N % 8 == 0 &&
+                   a.ldc % 8 == 0 && ld % 8 == 0 && reinterpret_cast<uintptr_t>(a.C) % 16 == 0 && reinterpret_cast<uintptr_t>(sp) % 16 == 0 &&
+                   (int64_t)256 * a.ldc * 2 < (1ll << 31) && (int64_t)256 * ld * 2 < (1ll << 31);
+      // WIDE epilogue (the kernel has it for bf16 in and out on 256-column tiles only).  Measured (tools/bench_ops.py --variants 2,32):
+      // +6…12 % on plain stores, a LOSS when a residual / aux operand must be fetched in the row-major layout too — those keep the
+      // accumulator-layout epilogue
+      c.wide_epi = tu.nt_wide_epi && !(a.flags & (LAKO_EPI_ATOMIC | LAKO_EPI_RESID | LAKO_EPI_AUXMASK)) && a.N % 8 == 0 &&
+                   a.ldc % 8 == 0 && reinterpret_cast<uintptr_t>(a.C) % 16 == 0;
+      if (rows == 256) {      // (the ticket-queue and eight-phase instantiations are 256-row)
+        if (tu.nt_queue) {
+          // several K-steps per tile to cover the ticket's round trip, several tiles per workgroup to be of any use, a persistent grid
+          const int tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
+          const int lds = c.side_lds ? nt_cfg_lds<T, 2, 4, 8, 4, true>() : nt_cfg_lds<T, 2, 4, 8, 4, false>();
+          c.queue = !(a.K * (int)sizeof(T) <= TKB || tiles <= nt_cfg_grid(tiles, lds, tu) || !tu.nt_persistent);
+        } else {
+          c.eight_phase = nt_pp_mode(tu, a);
+        }
+      }
+    }
+  }
+  if (kernel == NT_SKINNY) c.skinny_steps = nt_skinny_steps(a);
+  if (kernel == NT_SKINNY_NORM) c.skinny_steps = 4;      // (K <= 1 024: every K-step of a wave resident)
+  return c;
+}
 
 // the kernel for variant v (tuning gemm_nt_variant, or what nt_plan made of "auto") on the rows of `a`; kernels refuse what they do not take
 // by handing the call on: skinny → ring, four-wave / 192- / 288-row tiles → the eight-wave 256² kernel
@@ -2533,44 +2592,62 @@ NtPlan nt_plan(const NtArgs& a, const lako_tuning_t& tu) {
   return pl;
 }
 
+// the head rows of a tail split as a problem of their own
+inline NtArgs nt_head_from(NtArgs a, int64_t head_rows) {
+  a.M = (int)head_rows;
+  return a;
+}
+
+// nt_plan + the launcher-level decisions of its one or two launches: the whole plan, as lako_gemm_nt_plan reports it and launch_nt runs it
 template <typename T, typename TO>
-void launch_nt_kernel(NtKernel kernel, int rows, const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
+NtPlan nt_plan_full(const NtArgs& a, const lako_tuning_t& tu) {
+  NtPlan pl = nt_plan<T, TO>(a, tu);
+  if (pl.head_rows > 0) {
+    pl.head = nt_choice<T, TO>(NT_EIGHT, pl.head_tile, nt_head_from(a, pl.head_rows), tu);
+    pl.main = nt_choice<T, TO>(pl.kernel, pl.rows, nt_rows_from<T, TO>(a, pl.head_rows), tu);
+  } else {
+    pl.main = nt_choice<T, TO>(pl.kernel, pl.rows, a, tu);
+  }
+  return pl;
+}
+
+template <typename T, typename TO>
+void launch_nt_kernel(NtKernel kernel, int rows, const NtChoice& ch, const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
   switch (kernel) {
     case NT_FOUR: return rows == 192 ? launch_nt4<6>(a, tu, s) : launch_nt4<8>(a, tu, s);
     case NT_EIGHT:
       if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {
-        if (rows == 192) return launch_nt_256<T, TO, 6>(a, tu, s);
-        if (rows == 288) return launch_nt_256<T, TO, 9>(a, tu, s);
+        if (rows == 192) return launch_nt_256<T, TO, 6>(a, tu, ch, s);
+        if (rows == 288) return launch_nt_256<T, TO, 9>(a, tu, ch, s);
       }
-      return launch_nt_256<T, TO>(a, tu, s);
-    case NT_EIGHT_256x128: return launch_nt_cfg<T, TO, 4, 2, 4, 4>(a, tu, s);
-    case NT_FOUR_BY_128: return launch_nt_cfg<T, TO, 2, 2, 8, 8>(a, tu, s);
-    case NT_128: return launch_nt_cfg<T, TO, 2, 2, 4, 4>(a, tu, s);
+      return launch_nt_256<T, TO>(a, tu, ch, s);
+    case NT_EIGHT_256x128: return launch_nt_cfg<T, TO, 4, 2, 4, 4>(a, tu, ch, s);
+    case NT_FOUR_BY_128: return launch_nt_cfg<T, TO, 2, 2, 8, 8>(a, tu, ch, s);
+    case NT_128: return launch_nt_cfg<T, TO, 2, 2, 4, 4>(a, tu, ch, s);
     case NT_RING: return launch_nt_ring<T, TO>(a, s);
     case NT_SKINNY:
-      if constexpr (sizeof(T) == 2) rows == 16 ? launch_nt_skinny<TO, 1>(a, s) : rows == 64 ? launch_nt_skinny<TO, 4>(a, s) : launch_nt_skinny<TO, 2>(a, s);
+      if constexpr (sizeof(T) == 2)
+        rows == 16 ? launch_nt_skinny<TO, 1>(a, ch.skinny_steps, s) : rows == 64 ? launch_nt_skinny<TO, 4>(a, ch.skinny_steps, s) : launch_nt_skinny<TO, 2>(a, ch.skinny_steps, s);
       return;
     case NT_SKINNY_NORM:
       if constexpr (sizeof(T) == 2) launch_nt_skinny_norm<TO>(a, s);
       return;
+    case NT_FOUR_GATED: return launch_nt4_gated(a, s);
+    case NT_MX_FOUR:
+    case NT_MX_EIGHT:       // (lako_gemm_nt_mx launches its own)
     case NT_REFUSED: return;
   }
 }
 
-// LAKO_E_BADARG: no kernel takes the call, and nothing was launched (tests: test_gemm_nt_norm_refused_before_any_launch)
+// carries a plan of nt_plan_full out
 template <typename T, typename TO>
-int launch_nt(const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
-  const NtPlan pl = nt_plan<T, TO>(a, tu);
-  if (pl.kernel == NT_REFUSED) return LAKO_E_BADARG;
+void launch_nt(const NtPlan& pl, const NtArgs& a, const lako_tuning_t& tu, hipStream_t s) {
   if (pl.head_rows > 0) {
-    NtArgs head = a;
-    head.M = (int)pl.head_rows;
-    launch_nt_kernel<T, TO>(NT_EIGHT, pl.head_tile, head, tu, s);
-    launch_nt_kernel<T, TO>(pl.kernel, pl.rows, nt_rows_from<T, TO>(a, pl.head_rows), tu, s);
+    launch_nt_kernel<T, TO>(NT_EIGHT, pl.head_tile, pl.head, nt_head_from(a, pl.head_rows), tu, s);
+    launch_nt_kernel<T, TO>(pl.kernel, pl.rows, pl.main, nt_rows_from<T, TO>(a, pl.head_rows), tu, s);
   } else {
-    launch_nt_kernel<T, TO>(pl.kernel, pl.rows, a, tu, s);
+    launch_nt_kernel<T, TO>(pl.kernel, pl.rows, pl.main, a, tu, s);
   }
-  return 0;
 }
 
 template <typename T>
@@ -2597,7 +2674,18 @@ void launch_tn256(const TnArgs& a, const lako_tuning_t& tu, int grid, hipStream_
 
 }  // namespace
 
-extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
+// LAKO_CHECK_ALIGN names the function it stands in; the checks below stand for an entry point
+#define NT_CHECK_ALIGN(who, ptr, a)                                                   \
+  do {                                                                                \
+    if ((reinterpret_cast<uintptr_t>(ptr) % (a)) != 0) {                              \
+      lako_set_error("%s: pointer %s not %d-byte aligned", who, #ptr, (int)(a));      \
+      return LAKO_E_ALIGN;                                                            \
+    }                                                                                 \
+  } while (0)
+
+// The whole of lako_gemm_nt up to its first launch: validation, the kernel arguments, the plan.  No HIP call.  lako_gemm_nt launches what
+// this decides, lako_gemm_nt_plan reports it — one code path, so the two cannot disagree.  `tu_out`: the tuning the call runs under.
+static int nt_decide(const lako_gemm_nt_t* p, NtArgs& a, NtPlan& pl, const lako_tuning_t*& tu_out) {
   LAKO_CHECK_ARG(p != nullptr, "lako_gemm_nt: null params");
   LAKO_CHECK_ARG(p->M > 0 && p->N > 0 && p->K > 0, "lako_gemm_nt: bad dims M=%lld N=%lld K=%lld", (long long)p->M,
                  (long long)p->N, (long long)p->K);
@@ -2609,9 +2697,9 @@ extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
                  (long long)p->lda, (long long)p->ldb);
   LAKO_CHECK_ARG(p->N % 4 == 0 && p->ldc % 4 == 0, "lako_gemm_nt: N and ldc must be multiples of 4");
   LAKO_CHECK_ARG(p->M < (1 << 30) && p->N < (1 << 30) && p->K < (1 << 28), "lako_gemm_nt: dims too large");
-  LAKO_CHECK_ALIGN(p->A, 16);
-  LAKO_CHECK_ALIGN(p->B, 16);
-  LAKO_CHECK_ALIGN(p->C, 8);
+  NT_CHECK_ALIGN("lako_gemm_nt", p->A, 16);
+  NT_CHECK_ALIGN("lako_gemm_nt", p->B, 16);
+  NT_CHECK_ALIGN("lako_gemm_nt", p->C, 8);
   if (p->flags & LAKO_EPI_RESID) {
     LAKO_CHECK_ARG(p->resid != nullptr && p->ldr % 4 == 0, "lako_gemm_nt: RESID needs resid, ldr %% 4 == 0");
   }
@@ -2626,7 +2714,7 @@ extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
     return LAKO_E_UNSUPPORTED;
   }
   LAKO_CHECK_ARG(p->drop.p >= 0.f && p->drop.p < 1.f, "lako_gemm_nt: dropout p out of range");
-  NtArgs a = nt_args_from(p);
+  a = nt_args_from(p);
   if (p->flags & LAKO_EPI_NORM_A) {
     if (p->in_dtype != LAKO_BF16) {
       lako_set_error("lako_gemm_nt: LAKO_EPI_NORM_A is implemented for bf16 operands only");
@@ -2635,32 +2723,74 @@ extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
     LAKO_CHECK_ARG(p->norm_w != nullptr && p->norm_eps > 0.f, "lako_gemm_nt: NORM_A needs norm_w and norm_eps > 0");
     LAKO_CHECK_ARG(p->norm_out == nullptr || (p->norm_ld >= p->K && p->norm_ld % 8 == 0 && reinterpret_cast<uintptr_t>(p->norm_out) % 16 == 0),
                    "lako_gemm_nt: norm_out needs norm_ld >= K, norm_ld %% 8 == 0 and a 16-byte aligned pointer");
-    LAKO_CHECK_ALIGN(p->norm_w, 16);
+    NT_CHECK_ALIGN("lako_gemm_nt", p->norm_w, 16);
     a.norm_w = p->norm_w;
     a.norm_eps = p->norm_eps;
     a.norm_out = (char*)p->norm_out;
     a.norm_ld = p->norm_ld;
     a.norm_rs = p->norm_rstd;
   }
-  hipStream_t s = (hipStream_t)stream;
   const lako_tuning_t& tu = p->tuning ? *p->tuning : process_tuning();
+  tu_out = &tu;
   if (p->flags & (LAKO_EPI_GATED | LAKO_EPI_GATED_BWD)) {
-    launch_nt4_gated(a, s);
-    LAKO_LAUNCH_CHECK();
+    pl = NtPlan{NT_FOUR_GATED, 256};
     return LAKO_OK;
   }
-  int rc = 0;
   if (p->in_dtype == LAKO_BF16) {
-    if (p->out_dtype == LAKO_BF16) rc = launch_nt<bf16_t, bf16_t>(a, tu, s);
-    else rc = launch_nt<bf16_t, float>(a, tu, s);
+    if (p->out_dtype == LAKO_BF16) pl = nt_plan_full<bf16_t, bf16_t>(a, tu);
+    else pl = nt_plan_full<bf16_t, float>(a, tu);
   } else {
-    if (p->out_dtype == LAKO_BF16) rc = launch_nt<float, bf16_t>(a, tu, s);
-    else rc = launch_nt<float, float>(a, tu, s);
+    if (p->out_dtype == LAKO_BF16) pl = nt_plan_full<float, bf16_t>(a, tu);
+    else pl = nt_plan_full<float, float>(a, tu);
   }
-  if (rc != 0) {      // (nothing was launched)
+  if (pl.kernel == NT_REFUSED) {      // no kernel takes the call (tests: test_gemm_nt_norm_refused_before_any_launch)
     lako_set_error("lako_gemm_nt: LAKO_EPI_NORM_A is formed by the M <= 256 kernel only (bf16, K %% 32 == 0, K <= 1024, 16-byte aligned rows): M=%lld N=%lld K=%lld",
                    (long long)p->M, (long long)p->N, (long long)p->K);
     return LAKO_E_UNSUPPORTED;
+  }
+  return LAKO_OK;
+}
+
+static void nt_plan_out(const NtPlan& pl, lako_gemm_plan_t* out) {
+  *out = lako_gemm_plan_t{};
+  out->kernel = pl.kernel;
+  out->tile_rows = pl.rows;
+  out->head_rows = pl.head_rows;
+  out->head_tile = pl.head_tile;
+  out->side_lds = pl.main.side_lds;
+  out->wide_epi = pl.main.wide_epi;
+  out->queue = pl.main.queue;
+  out->eight_phase = pl.main.eight_phase;
+  out->skinny_steps = pl.main.skinny_steps;
+  out->head_side_lds = pl.head.side_lds;
+  out->head_wide_epi = pl.head.wide_epi;
+  out->head_queue = pl.head.queue;
+  out->head_eight_phase = pl.head.eight_phase;
+}
+
+extern "C" int lako_gemm_nt_plan(const lako_gemm_nt_t* p, lako_gemm_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_gemm_nt_plan: null out");
+  *out = lako_gemm_plan_t{};
+  NtArgs a{};
+  NtPlan pl{};
+  const lako_tuning_t* tu = nullptr;
+  if (const int rc = nt_decide(p, a, pl, tu)) return rc;
+  nt_plan_out(pl, out);
+  return LAKO_OK;
+}
+
+extern "C" int lako_gemm_nt(const lako_gemm_nt_t* p, lako_stream_t stream) {
+  NtArgs a{};
+  NtPlan pl{};
+  const lako_tuning_t* tu = nullptr;
+  if (const int rc = nt_decide(p, a, pl, tu)) return rc;      // (nothing was launched)
+  hipStream_t s = (hipStream_t)stream;
+  if (p->in_dtype == LAKO_BF16) {
+    if (p->out_dtype == LAKO_BF16) launch_nt<bf16_t, bf16_t>(pl, a, *tu, s);
+    else launch_nt<bf16_t, float>(pl, a, *tu, s);
+  } else {
+    if (p->out_dtype == LAKO_BF16) launch_nt<float, bf16_t>(pl, a, *tu, s);
+    else launch_nt<float, float>(pl, a, *tu, s);
   }
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
@@ -2707,8 +2837,15 @@ static int tn_check_item(const char* who, int item, const lako_gemm_tn_item_t& p
   return LAKO_OK;
 }
 
-// one problem (lako_gemm_tn, and the items of a grouped call that the grouped 256² launch does not take)
-static int tn_single(const lako_gemm_tn_item_t& p, int64_t K, int in_dtype, int split_k, const lako_tuning_t& tu, hipStream_t s) {
+// one problem (lako_gemm_tn, and the items of a grouped call that the grouped 256² launch does not take): everything up to the launch —
+// validation, the kernel arguments, the K-split.  No HIP call: tn_single launches what this decides, the plan queries report it.
+struct TnSinglePlan {
+  bool big;          // the 256² kernel (launch_tn256 on `grid` workgroups), else gemm_tn_kernel
+  bool zero_first;   // the small-tile kernel only adds: overwrite = zero, then add
+  bool bf16;
+  int grid;
+};
+static int tn_single_decide(const lako_gemm_tn_item_t& p, int64_t K, int in_dtype, int split_k, const lako_tuning_t& tu, TnArgs& a, TnSinglePlan& d) {
   LAKO_CHECK_ARG(p.M > 0 && p.N > 0 && K > 0, "lako_gemm_tn: bad dims");
   LAKO_CHECK_ARG(split_k >= -2, "lako_gemm_tn: split_k %d", split_k);
   const int out_mode = split_k < 0 ? -split_k : 0;      // -1: exclusive read-modify-write, -2: overwrite (one K-split either way)
@@ -2719,7 +2856,9 @@ static int tn_single(const lako_gemm_tn_item_t& p, int64_t K, int in_dtype, int 
   const int esz = in_dtype == LAKO_F32 ? 4 : 2;
   if (const int rc = tn_check_item("lako_gemm_tn", -1, p, esz)) return rc;
   const int64_t M = p.M, N = p.N;
-  TnArgs a{};      // (n_items 0: one problem; no slabs)
+  a = TnArgs{};      // (n_items 0: one problem; no slabs)
+  d = TnSinglePlan{};
+  d.bf16 = in_dtype == LAKO_BF16;
   a.A = (const char*)p.a; a.B = (const char*)p.b; a.C = p.c; a.M = (int)M; a.N = (int)N; a.K = (int)K;
   a.lda = p.lda; a.ldb = p.ldb; a.ldc = p.ldc; a.alpha = p.alpha;
   a.Mout = p.rows_out > 0 ? p.rows_out : (int)M;      // rows_out: 0 = M, else only the first rows_out rows of C are written
@@ -2742,18 +2881,13 @@ static int tn_single(const lako_gemm_tn_item_t& p, int64_t K, int in_dtype, int 
     a.no_stagger = 1;      // (as the grouped launch: see lako_gemm_tn_grouped)
     a.out_mode = a.split_k == 1 ? out_mode : 0;
     a.wide_out = reinterpret_cast<uintptr_t>(p.c) % 16 == 0 && p.ldc % 4 == 0 && N % 4 == 0;
-    launch_tn256(a, tu, tiles * a.split_k, s);
-    LAKO_LAUNCH_CHECK();
+    d.big = true;
+    d.grid = tiles * a.split_k;
     return LAKO_OK;
   }
   a.tiles_m = cdiv(M, TM);
   a.tiles_n = cdiv(N, TN_);
-  if (out_mode == 2) {      // the small-tile kernel only adds: overwrite = zero, then add
-    if (hipMemset2DAsync(p.c, (size_t)p.ldc * 4, 0, (size_t)N * 4, (size_t)a.Mout, s) != hipSuccess) {
-      lako_set_error("lako_gemm_tn: could not zero the output");
-      return LAKO_E_LAUNCH;
-    }
-  }
+  d.zero_first = out_mode == 2;
   const int kr = in_dtype == LAKO_BF16 ? 64 : 32;
   if (split_k <= 0) {  // auto: aim at >= 2 workgroups per CU, at least 4 K-steps per split
     split_k = cdiv(512, a.tiles_m * a.tiles_n);
@@ -2763,10 +2897,45 @@ static int tn_single(const lako_gemm_tn_item_t& p, int64_t K, int in_dtype, int 
   }
   a.k_chunk = cdiv(cdiv(K, split_k), kr) * kr;
   a.split_k = cdiv(K, a.k_chunk);
-  if (in_dtype == LAKO_BF16) launch_tn<bf16_t>(a, s);
+  d.grid = a.tiles_m * a.tiles_n * a.split_k;
+  return LAKO_OK;
+}
+
+static int tn_single_launch(const TnArgs& a, const TnSinglePlan& d, const lako_tuning_t& tu, hipStream_t s) {
+  if (d.big) {
+    launch_tn256(a, tu, d.grid, s);
+    LAKO_LAUNCH_CHECK();
+    return LAKO_OK;
+  }
+  if (d.zero_first) {
+    if (hipMemset2DAsync(a.C, (size_t)a.ldc * 4, 0, (size_t)a.N * 4, (size_t)a.Mout, s) != hipSuccess) {
+      lako_set_error("lako_gemm_tn: could not zero the output");
+      return LAKO_E_LAUNCH;
+    }
+  }
+  if (d.bf16) launch_tn<bf16_t>(a, s);
   else launch_tn<float>(a, s);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
+}
+
+static int tn_single(const lako_gemm_tn_item_t& p, int64_t K, int in_dtype, int split_k, const lako_tuning_t& tu, hipStream_t s) {
+  TnArgs a;
+  TnSinglePlan d;
+  if (const int rc = tn_single_decide(p, K, in_dtype, split_k, tu, a, d)) return rc;
+  return tn_single_launch(a, d, tu, s);
+}
+
+// what a plan query says of one problem's launch
+static void tn_single_plan_out(const TnArgs& a, const TnSinglePlan& d, const lako_tuning_t& tu, lako_gemm_tn_plan_t* out) {
+  out->big = d.big;
+  out->four = d.big && tn4_ok(a, tu);
+  out->tiles = a.tiles_m * a.tiles_n;
+  out->split_k = a.split_k;
+  out->k_chunk = a.k_chunk;
+  out->out_mode = d.big ? a.out_mode : 0;
+  out->atomics = !(d.big && a.out_mode != 0);
+  out->grid = d.grid;
 }
 
 extern "C" int lako_gemm_tn(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda,
@@ -2774,6 +2943,19 @@ extern "C" int lako_gemm_tn(const void* A, const void* B, float* C, int64_t M, i
                             lako_stream_t stream) {
   const lako_gemm_tn_item_t p = {A, B, C, M, N, lda, ldb, ldc, alpha, 0};
   return tn_single(p, K, in_dtype, split_k, tuning ? *tuning : process_tuning(), (hipStream_t)stream);
+}
+
+extern "C" int lako_gemm_tn_plan(const void* A, const void* B, float* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                                 int in_dtype, float alpha, int split_k, const lako_tuning_t* tuning, lako_gemm_tn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_gemm_tn_plan: null out");
+  *out = lako_gemm_tn_plan_t{};
+  const lako_tuning_t& tu = tuning ? *tuning : process_tuning();
+  const lako_gemm_tn_item_t p = {A, B, C, M, N, lda, ldb, ldc, alpha, 0};
+  TnArgs a;
+  TnSinglePlan d;
+  if (const int rc = tn_single_decide(p, K, in_dtype, split_k, tu, a, d)) return rc;
+  tn_single_plan_out(a, d, tu, out);
+  return LAKO_OK;
 }
 
 // ---- the grouped TN plan: how one launch of the 256² weight-gradient kernels cuts K.  Reads its arguments (and LAKO_DETERMINISTIC) and
@@ -2841,10 +3023,25 @@ extern "C" int64_t lako_gemm_tn_grouped_workspace(const lako_gemm_tn_item_t* ite
   return pl.slab_bytes + pl.tick_bytes;
 }
 
-extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k,
-                                    const lako_tuning_t* tuning, void* workspace, int64_t workspace_bytes, lako_stream_t stream) {
-  const lako_tuning_t& tu = tuning ? *tuning : process_tuning();
-  hipStream_t s = (hipStream_t)stream;
+// lako_gemm_tn_grouped up to its first launch: validation, the kernel arguments, the K-cut (tn_grouped_plan), slabs or atomics.  No HIP call.
+// per_item: shapes the 256×256 kernel does not take — one tn_single per problem (each decided by tn_single_decide), `a` is not filled.
+struct TnGroupedDecision {
+  bool per_item;
+  bool use_slabs;       // the K-splits meet through the caller's workspace (its tickets are zeroed before the launch)
+  int64_t tick_bytes;
+  int tiles, grid;
+};
+// (deterministic mode without slabs: one contributor per element) … and the grid; after tn_grouped_decide, and again should the tickets' memset fail
+static void tn_grouped_finish(TnArgs& a, TnGroupedDecision& d, int64_t K) {
+  if (lako_det::on() && a.split_k > 1 && a.slabs == nullptr) {      // (no workspace: one contributor per element)
+    a.split_k = 1;
+    a.k_chunk = cdiv(K, 64) * 64;
+  }
+  d.grid = a.t_full > 0 ? 8 * (a.t_full / 8 + cdiv((int64_t)(d.tiles - a.t_full) * a.split_k, 8)) : d.tiles * a.split_k;
+}
+static int tn_grouped_decide(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k, const lako_tuning_t& tu,
+                             void* workspace, int64_t workspace_bytes, TnArgs& a, TnGroupedDecision& d) {
+  d = TnGroupedDecision{};
   LAKO_CHECK_ARG(items && n_items >= 1 && n_items <= LAKO_TN_GROUP_MAX, "lako_gemm_tn_grouped: 1..%d items", LAKO_TN_GROUP_MAX);
   LAKO_CHECK_ARG(split_k >= -3, "lako_gemm_tn_grouped: split_k %d", split_k);
   LAKO_CHECK_ARG(K > 0 && K < (1 << 30), "lako_gemm_tn_grouped: bad K");
@@ -2872,13 +3069,15 @@ extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_item
     }
   }
   if (!tn_grouped_is_big(items, n_items, in_dtype, tu)) {   // shapes the 256×256 kernel does not take: one launch per problem
-    for (int i = 0; i < n_items; ++i) {
-      const int rc = tn_single(items[i], K, in_dtype, split_k == -3 ? 0 : split_k, tu, s);
-      if (rc != LAKO_OK) return rc;
+    d.per_item = true;
+    for (int i = 0; i < n_items; ++i) {      // every item is checked before the first is launched
+      TnArgs ai;
+      TnSinglePlan di;
+      if (const int rc = tn_single_decide(items[i], K, in_dtype, split_k == -3 ? 0 : split_k, tu, ai, di)) return rc;
     }
     return LAKO_OK;
   }
-  TnArgs a{};
+  a = TnArgs{};
   a.n_items = n_items;
   a.K = (int)K;
   a.no_atomics = tu.tn_big == 2;
@@ -2888,13 +3087,13 @@ extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_item
   for (int i = 0; i < n_items; ++i) {
     const lako_gemm_tn_item_t& p = items[i];
     if (const int rc = tn_check_item("lako_gemm_tn_grouped", i, p, 2)) return rc;
-    TnArgs::Item& d = a.items[i];
-    d.A = (const char*)p.a; d.B = (const char*)p.b; d.C = p.c; d.M = (int)p.M; d.N = (int)p.N;
-    d.lda = p.lda; d.ldb = p.ldb; d.ldc = p.ldc; d.alpha = p.alpha;
-    d.Mout = p.rows_out > 0 ? p.rows_out : (int)p.M;
-    d.tiles_n = cdiv((int)p.N, 256);
-    d.tile_start = tiles;
-    tiles += cdiv((int)p.M, 256) * d.tiles_n;
+    TnArgs::Item& it = a.items[i];
+    it.A = (const char*)p.a; it.B = (const char*)p.b; it.C = p.c; it.M = (int)p.M; it.N = (int)p.N;
+    it.lda = p.lda; it.ldb = p.ldb; it.ldc = p.ldc; it.alpha = p.alpha;
+    it.Mout = p.rows_out > 0 ? p.rows_out : (int)p.M;
+    it.tiles_n = cdiv((int)p.N, 256);
+    it.tile_start = tiles;
+    tiles += cdiv((int)p.M, 256) * it.tiles_n;
     if (reinterpret_cast<uintptr_t>(p.c) % 16 != 0 || p.ldc % 4 != 0 || p.N % 4 != 0) a.wide_out = 0;
   }
   // every wave issues its DMA at the top of the K-step (round 4, with the full-K units: 7.29 -> 7.04 ms per step against waves 4-7 issuing
@@ -2903,6 +3102,7 @@ extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_item
   a.no_stagger = !tn_stag;
   a.tiles_m = tiles;     // the kernel only uses the product
   a.tiles_n = 1;
+  d.tiles = tiles;
   const TnGroupedPlan pl = tn_grouped_plan(items, n_items, K, split_k, tu);
   a.t_full = pl.t_full;
   a.split_k = pl.split_k;
@@ -2911,18 +3111,64 @@ extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_item
   if (pl.slabs && workspace != nullptr && workspace_bytes >= pl.slab_bytes + pl.tick_bytes && reinterpret_cast<uintptr_t>(workspace) % 16 == 0) {
     a.slabs = reinterpret_cast<float*>(workspace);
     a.tickets = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + pl.slab_bytes);
-    if (hipMemsetAsync(a.tickets, 0, (size_t)pl.tick_bytes, s) != hipSuccess) {
-      (void)hipGetLastError();
-      a.slabs = nullptr;
-      a.tickets = nullptr;
+    d.use_slabs = true;
+    d.tick_bytes = pl.tick_bytes;
+  }
+  tn_grouped_finish(a, d, K);
+  return LAKO_OK;
+}
+
+extern "C" int lako_gemm_tn_grouped_plan(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k,
+                                         const lako_tuning_t* tuning, void* workspace, int64_t workspace_bytes, lako_gemm_tn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_gemm_tn_grouped_plan: null out");
+  *out = lako_gemm_tn_plan_t{};
+  const lako_tuning_t& tu = tuning ? *tuning : process_tuning();
+  static thread_local TnArgs a;      // (5 KiB of items)
+  TnGroupedDecision d;
+  if (const int rc = tn_grouped_decide(items, n_items, K, in_dtype, split_k, tu, workspace, workspace_bytes, a, d)) return rc;
+  if (d.per_item) {
+    TnSinglePlan d0;
+    (void)tn_single_decide(items[0], K, in_dtype, split_k == -3 ? 0 : split_k, tu, a, d0);
+    tn_single_plan_out(a, d0, tu, out);
+    out->per_item = 1;
+    return LAKO_OK;
+  }
+  out->big = 1;
+  out->four = tn4_ok(a, tu);
+  out->tiles = d.tiles;
+  out->split_k = a.split_k;
+  out->k_chunk = a.k_chunk;
+  out->full_tiles = a.t_full;
+  out->slabs = d.use_slabs;
+  out->out_mode = a.out_mode;
+  // pieces add by atomics unless they meet in slabs or the tile has one contributor under an exclusive mode; of a hybrid launch only the
+  // tiles after full_tiles
+  out->atomics = !d.use_slabs && a.out_mode == 0 && a.t_full < d.tiles;
+  out->grid = d.grid;
+  return LAKO_OK;
+}
+
+extern "C" int lako_gemm_tn_grouped(const lako_gemm_tn_item_t* items, int n_items, int64_t K, int in_dtype, int split_k,
+                                    const lako_tuning_t* tuning, void* workspace, int64_t workspace_bytes, lako_stream_t stream) {
+  const lako_tuning_t& tu = tuning ? *tuning : process_tuning();
+  hipStream_t s = (hipStream_t)stream;
+  TnArgs a;
+  TnGroupedDecision d;
+  if (const int rc = tn_grouped_decide(items, n_items, K, in_dtype, split_k, tu, workspace, workspace_bytes, a, d)) return rc;
+  if (d.per_item) {
+    for (int i = 0; i < n_items; ++i) {
+      const int rc = tn_single(items[i], K, in_dtype, split_k == -3 ? 0 : split_k, tu, s);
+      if (rc != LAKO_OK) return rc;
     }
+    return LAKO_OK;
   }
-  if (lako_det::on() && a.split_k > 1 && a.slabs == nullptr) {      // (no workspace: one contributor per element)
-    a.split_k = 1;
-    a.k_chunk = cdiv(K, 64) * 64;
+  if (d.use_slabs && hipMemsetAsync(a.tickets, 0, (size_t)d.tick_bytes, s) != hipSuccess) {
+    (void)hipGetLastError();
+    a.slabs = nullptr;
+    a.tickets = nullptr;
+    tn_grouped_finish(a, d, K);
   }
-  const int grid = a.t_full > 0 ? 8 * (a.t_full / 8 + cdiv((int64_t)(tiles - a.t_full) * a.split_k, 8)) : tiles * a.split_k;
-  launch_tn256(a, tu, grid, s);
+  launch_tn256(a, tu, d.grid, s);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }
@@ -2942,7 +3188,8 @@ extern "C" int lako_mx_quantize(const void* x, int64_t rows, int64_t K, int64_t 
   return LAKO_OK;
 }
 
-extern "C" int lako_gemm_nt_mx(const lako_gemm_nt_t* p, const uint8_t* a_scales, const uint8_t* b_scales, lako_stream_t stream) {
+// lako_gemm_nt_mx up to its launch: validation, the kernel arguments, four-wave or eight-wave.  No HIP call.
+static int mx_decide(const lako_gemm_nt_t* p, const uint8_t* a_scales, const uint8_t* b_scales, MxArgs& m, NtPlan& pl) {
   LAKO_CHECK_ARG(p != nullptr && a_scales && b_scales, "lako_gemm_nt_mx: null params");
   LAKO_CHECK_ARG(p->M > 0 && p->N > 0 && p->K > 0, "lako_gemm_nt_mx: bad dims");
   LAKO_CHECK_ARG(p->in_dtype == LAKO_FP8_E4M3 && p->out_dtype == LAKO_BF16, "lako_gemm_nt_mx: e4m3 operands, bf16 output");
@@ -2950,16 +3197,14 @@ extern "C" int lako_gemm_nt_mx(const lako_gemm_nt_t* p, const uint8_t* a_scales,
   LAKO_CHECK_ARG(p->N % 8 == 0 && p->ldc % 8 == 0, "lako_gemm_nt_mx: N and ldc must be multiples of 8");
   LAKO_CHECK_ARG(p->M < (1 << 30) && p->N < (1 << 30) && p->K < (1 << 24), "lako_gemm_nt_mx: dims too large");
   LAKO_CHECK_ARG(!(p->flags & LAKO_EPI_ATOMIC), "lako_gemm_nt_mx: no atomic epilogue");
-  LAKO_CHECK_ALIGN(p->A, 16);
-  LAKO_CHECK_ALIGN(p->B, 16);
-  LAKO_CHECK_ALIGN(p->C, 16);
-  LAKO_CHECK_ALIGN(a_scales, 4);
-  LAKO_CHECK_ALIGN(b_scales, 4);
+  NT_CHECK_ALIGN("lako_gemm_nt_mx", p->A, 16);
+  NT_CHECK_ALIGN("lako_gemm_nt_mx", p->B, 16);
+  NT_CHECK_ALIGN("lako_gemm_nt_mx", p->C, 16);
+  NT_CHECK_ALIGN("lako_gemm_nt_mx", a_scales, 4);
+  NT_CHECK_ALIGN("lako_gemm_nt_mx", b_scales, 4);
   if (p->flags & LAKO_EPI_RESID) LAKO_CHECK_ARG(p->resid != nullptr && p->ldr % 4 == 0, "lako_gemm_nt_mx: RESID needs resid, ldr %% 4 == 0");
   if (p->flags & LAKO_EPI_AUXMASK) LAKO_CHECK_ARG(p->aux != nullptr && p->ldaux % 4 == 0, "lako_gemm_nt_mx: AUXMASK needs aux (bf16), ldaux %% 4 == 0");
-  hipStream_t s = (hipStream_t)stream;
   const lako_tuning_t& tu = p->tuning ? *p->tuning : process_tuning();
-  MxArgs m;
   NtArgs& a = m.nt;
   a = nt_args_from(p);
   a.tiles_m = cdiv(a.M, 256);
@@ -2968,25 +3213,53 @@ extern "C" int lako_gemm_nt_mx(const lako_gemm_nt_t* p, const uint8_t* a_scales,
   m.sa = a_scales;
   m.sb = b_scales;
   m.ksp = (int)(((p->K / 128) + 3) / 4 * 4);
+  pl = NtPlan{};
   // round 6: the four-wave tile with two K-slices in flight (gemm_nt4_mx.h) where it applies — whole groups of four K-steps, at least one
   // round of the chip, the epilogues and 32-bit offsets of nt4_epilogue_ok (the ticket queue does not concern this kernel: nt_queue is not
   // consulted); the tile height by the rounds of the chip as for bf16, or forced by variants 3 / 9
   if (tu.nt_four && a.K % 512 == 0 && (int64_t)a.tiles_m * a.tiles_n >= 256 && nt4_epilogue_ok(a, 1)) {
     const bool six = tu.nt_variant == 3 || (tu.nt_variant != 9 && nt4_prefers_192(a.M, a.N, a.K / 128, 1.6, 1.25));
-    const bool side = a.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
     a.tiles_m = cdiv(a.M, six ? 192 : 256);
     a.group_m = nt_group_m(tu, a.tiles_n);
     a.dephase = 0;
     a.epi_direct = 0;
-    if (six) side ? launch_nt4_mx_kernel<6, true>(m, s) : launch_nt4_mx_kernel<6, false>(m, s);
-    else side ? launch_nt4_mx_kernel<8, true>(m, s) : launch_nt4_mx_kernel<8, false>(m, s);
-    LAKO_LAUNCH_CHECK();
+    pl.kernel = NT_MX_FOUR;
+    pl.rows = six ? 192 : 256;
     return LAKO_OK;
   }
   // the eight-wave kernel bands from 16 tile columns on
   a.group_m = nt_group_m(tu, a.tiles_n, 16);
   const int grid = std::min(a.tiles_m * a.tiles_n, 256);
   a.dephase = a.tiles_m * a.tiles_n > grid ? nt_dephase_word(tu) : 0;
+  pl.kernel = NT_MX_EIGHT;
+  pl.rows = 256;
+  pl.main.wide_epi = a.wide_epi;
+  return LAKO_OK;
+}
+
+extern "C" int lako_gemm_nt_mx_plan(const lako_gemm_nt_t* p, const uint8_t* a_scales, const uint8_t* b_scales, lako_gemm_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_gemm_nt_mx_plan: null out");
+  *out = lako_gemm_plan_t{};
+  MxArgs m;
+  NtPlan pl{};
+  if (const int rc = mx_decide(p, a_scales, b_scales, m, pl)) return rc;
+  nt_plan_out(pl, out);
+  return LAKO_OK;
+}
+
+extern "C" int lako_gemm_nt_mx(const lako_gemm_nt_t* p, const uint8_t* a_scales, const uint8_t* b_scales, lako_stream_t stream) {
+  MxArgs m;
+  NtPlan pl{};
+  if (const int rc = mx_decide(p, a_scales, b_scales, m, pl)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (pl.kernel == NT_MX_FOUR) {
+    const bool six = pl.rows == 192, side = m.nt.flags & (LAKO_EPI_RESID | LAKO_EPI_AUXMASK);
+    if (six) side ? launch_nt4_mx_kernel<6, true>(m, s) : launch_nt4_mx_kernel<6, false>(m, s);
+    else side ? launch_nt4_mx_kernel<8, true>(m, s) : launch_nt4_mx_kernel<8, false>(m, s);
+    LAKO_LAUNCH_CHECK();
+    return LAKO_OK;
+  }
+  const int grid = std::min(m.nt.tiles_m * m.nt.tiles_n, 256);
   constexpr int LDS = 2 * (256 + 256) * TKB;
   LAKO_SET_MAX_LDS((&gemm_nt_mx_kernel), LDS);
   hipLaunchKernelGGL(gemm_nt_mx_kernel, dim3(grid), dim3(512), LDS, s, m);

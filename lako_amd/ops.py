@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import (EPI_ATOMIC, EPI_AUXMASK, EPI_GATED, EPI_GATED_BWD, EPI_NORM_A, EPI_RELU, EPI_RESID, LAKO_BF16, LAKO_F32, LAKO_FP8_E4M3, AttnBwd, AttnFwd, Dropout,
-                   GemmNT, LakoError, NO_DROP, check)
+                   GemmNT, GemmPlan, GemmTNPlan, LakoError, NO_DROP, check)
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -124,8 +124,8 @@ class HipOps:
             raise LakoError("mx_quantize: x bf16 [rows, K], q uint8 [rows, K], scales uint8 [rows, mx_scale_cols(K)], all contiguous rows")
         self._timed("mx_quantize", 0.0, lambda: check(self.lib.lako_mx_quantize(_p(x), rows, K, ld, _p(q), _p(scales), self._stream()), "lako_mx_quantize"))
 
-    def gemm_nt_mx(self, Aq, As, Bq, Bs, Cm, *, alpha=1.0, relu=False, resid=None, aux=None, aux_scale=1.0, drop=None):
-        """C bf16 [M, N] = epilogue(alpha · dequant(Aq, As) · dequant(Bq, Bs)ᵀ) on the block-scaled fp8 matrix cores"""
+    def _gemm_nt_mx_struct(self, Aq, As, Bq, Bs, Cm, alpha, relu, resid, aux, aux_scale, drop):
+        """the lako_gemm_nt_t of an MX product: what gemm_nt_mx launches and gemm_nt_mx_plan asks about"""
         M, K, lda = _rowmajor2d(Aq, "gemm_nt_mx A")
         N, K2, ldb = _rowmajor2d(Bq, "gemm_nt_mx B")
         M2, N2, ldc = _rowmajor2d(Cm, "gemm_nt_mx C")
@@ -151,7 +151,19 @@ class HipOps:
         p.aux_scale = float(aux_scale)
         p.drop = _drop(drop)
         p.tuning = self._tuning_p
-        self._timed("gemm_nt_mx", 2.0 * M * N * K, lambda: check(self.lib.lako_gemm_nt_mx(C.byref(p), _p(As), _p(Bs), self._stream()), "lako_gemm_nt_mx"))
+        return p
+
+    def gemm_nt_mx(self, Aq, As, Bq, Bs, Cm, *, alpha=1.0, relu=False, resid=None, aux=None, aux_scale=1.0, drop=None):
+        """C bf16 [M, N] = epilogue(alpha · dequant(Aq, As) · dequant(Bq, Bs)ᵀ) on the block-scaled fp8 matrix cores"""
+        p = self._gemm_nt_mx_struct(Aq, As, Bq, Bs, Cm, alpha, relu, resid, aux, aux_scale, drop)
+        self._timed("gemm_nt_mx", 2.0 * p.M * p.N * p.K, lambda: check(self.lib.lako_gemm_nt_mx(C.byref(p), _p(As), _p(Bs), self._stream()), "lako_gemm_nt_mx"))
+
+    def gemm_nt_mx_plan(self, Aq, As, Bq, Bs, Cm, *, alpha=1.0, relu=False, resid=None, aux=None, aux_scale=1.0, drop=None):
+        """the kernel gemm_nt_mx would run for these arguments (lako_gemm_nt_mx_plan: the same struct, nothing launched)"""
+        p = self._gemm_nt_mx_struct(Aq, As, Bq, Bs, Cm, alpha, relu, resid, aux, aux_scale, drop)
+        out = GemmPlan()
+        check(self.lib.lako_gemm_nt_mx_plan(C.byref(p), _p(As), _p(Bs), C.byref(out)), "lako_gemm_nt_mx_plan")
+        return out
 
     # ---- GEMMs -----------------------------------------------------------------------------
     def gemm_nt(self, A, B, Cm, *, alpha=1.0, relu=False, resid=None, aux=None, aux_scale=1.0, drop=None,
@@ -169,7 +181,8 @@ class HipOps:
         if rc != 0:
             check(rc, "lako_gemm_nt")
 
-    def _gemm_nt_call(self, A, B, Cm, alpha, relu, resid, aux, aux_scale, drop, atomic, norm):
+    def _gemm_nt_struct(self, A, B, Cm, alpha, relu, resid, aux, aux_scale, drop, atomic, norm):
+        """the lako_gemm_nt_t of a product: what _gemm_nt_call launches and gemm_nt_plan asks about"""
         M, K, lda = _rowmajor2d(A, "gemm_nt A")
         N, K2, ldb = _rowmajor2d(B, "gemm_nt B")
         M2, N2, ldc = _rowmajor2d(Cm, "gemm_nt C")
@@ -199,6 +212,22 @@ class HipOps:
                     rstd.dtype != torch.float32 or rstd.numel() != M:
                 raise LakoError("gemm_nt: norm = (w fp32 [K], eps, xn like A, rstd fp32 [M])")
             p.norm_w, p.norm_eps, p.norm_out, p.norm_ld, p.norm_rstd = _p(w), float(eps), _p(xn), xn.stride(0), _p(rstd)
+        return p
+
+    def gemm_nt_plan(self, A, B, Cm, *, alpha=1.0, relu=False, resid=None, aux=None, aux_scale=1.0, drop=None, atomic=False, norm=None):
+        """the kernel(s) gemm_nt would run for these arguments under this object's tuning (lako_gemm_nt_plan: the same struct, nothing
+        launched).  A call the library refuses with LAKO_E_UNSUPPORTED (norm= on a shape the M <= 256 kernel does not take: gemm_nt then
+        runs the norm as its own launch) comes back with kernel NT_REFUSED."""
+        p = self._gemm_nt_struct(A, B, Cm, alpha, relu, resid, aux, aux_scale, drop, atomic, norm)
+        out = GemmPlan()
+        rc = self.lib.lako_gemm_nt_plan(C.byref(p), C.byref(out))
+        if rc != 0 and rc != -4:
+            check(rc, "lako_gemm_nt_plan")
+        return out
+
+    def _gemm_nt_call(self, A, B, Cm, alpha, relu, resid, aux, aux_scale, drop, atomic, norm):
+        p = self._gemm_nt_struct(A, B, Cm, alpha, relu, resid, aux, aux_scale, drop, atomic, norm)
+        M, N, K = p.M, p.N, p.K
         # probe classes follow the kernel the library picks: M <= 256 rows (the decoder) runs on the split-K / ring kernels
         rc = [0]
 
@@ -228,10 +257,8 @@ class HipOps:
         finally:
             self.tuning.nt_variant = old
 
-    def gemm_nt_gated(self, A, B, Cm, side, drop=None, backward=False):
-        """forward (backward=False): A = xn [M, d], B = [Wi0; Wi1] [2f, d] → Cm = pre [M, 2f] and side = h [M, f] =
-        lako_gated_gelu_fwd(pre, drop) in one launch.  backward: A = dy [M, d], B = Woᵀ [f, d] → Cm = dpre [M, 2f] =
-        lako_gated_gelu_bwd(bf16(A·Bᵀ), side = pre, drop); the product itself is not stored.  Bit-identical to the two-launch forms."""
+    def _gemm_nt_gated_struct(self, A, B, Cm, side, drop, backward):
+        """the lako_gemm_nt_t of a fused gated product: what gemm_nt_gated launches and gemm_nt_gated_plan asks about"""
         M, K, lda = _rowmajor2d(A, "gemm_nt_gated A")
         N, K2, ldb = _rowmajor2d(B, "gemm_nt_gated B")
         f = N // 2 if not backward else N
@@ -245,10 +272,28 @@ class HipOps:
         p.alpha, p.flags, p.aux_scale = 1.0, (EPI_GATED_BWD if backward else EPI_GATED), 1.0
         p.drop = _drop(drop)
         p.tuning = self._tuning_p
-        self._timed(f"gemm_nt_gated{'_bwd' if backward else ''}", 2.0 * M * N * K,
+        return p
+
+    def gemm_nt_gated_plan(self, A, B, Cm, side, drop=None, backward=False):
+        """the plan of gemm_nt_gated (NT_FOUR_GATED), or kernel NT_REFUSED where the library refuses the fused epilogue with
+        LAKO_E_UNSUPPORTED — the condition gated_fused_ok mirrors for the engine"""
+        p = self._gemm_nt_gated_struct(A, B, Cm, side, drop, backward)
+        out = GemmPlan()
+        rc = self.lib.lako_gemm_nt_plan(C.byref(p), C.byref(out))
+        if rc != 0 and rc != -4:
+            check(rc, "lako_gemm_nt_plan (gated)")
+        return out
+
+    def gemm_nt_gated(self, A, B, Cm, side, drop=None, backward=False):
+        """forward (backward=False): A = xn [M, d], B = [Wi0; Wi1] [2f, d] → Cm = pre [M, 2f] and side = h [M, f] =
+        lako_gated_gelu_fwd(pre, drop) in one launch.  backward: A = dy [M, d], B = Woᵀ [f, d] → Cm = dpre [M, 2f] =
+        lako_gated_gelu_bwd(bf16(A·Bᵀ), side = pre, drop); the product itself is not stored.  Bit-identical to the two-launch forms."""
+        p = self._gemm_nt_gated_struct(A, B, Cm, side, drop, backward)
+        self._timed(f"gemm_nt_gated{'_bwd' if backward else ''}", 2.0 * p.M * p.N * p.K,
                     lambda: check(self.lib.lako_gemm_nt(C.byref(p), self._stream()), "lako_gemm_nt (gated)"))
 
-    def gemm_tn(self, A, B, Cm, *, alpha=1.0, split_k=0):
+    def _gemm_tn_args(self, A, B, Cm, alpha, split_k):
+        """the argument list lako_gemm_tn and lako_gemm_tn_plan share (up to the tuning)"""
         K, M, lda = _rowmajor2d(A, "gemm_tn A")
         K2, N, ldb = _rowmajor2d(B, "gemm_tn B")
         M2, N2, ldc = _rowmajor2d(Cm, "gemm_tn C")
@@ -256,14 +301,39 @@ class HipOps:
             raise LakoError(f"gemm_tn: shape/dtype mismatch A{tuple(A.shape)} B{tuple(B.shape)} C{tuple(Cm.shape)}")
         if self.det and split_k == 0:
             split_k = 1
-        self._timed("gemm_tn", 2.0 * M * N * K, lambda: check(self.lib.lako_gemm_tn(_p(A), _p(B), _p(Cm), M, N, K, lda, ldb, ldc, _dt(A), float(alpha), int(split_k),
-                                    self._tuning_p, self._stream()), "lako_gemm_tn"))
+        return (_p(A), _p(B), _p(Cm), M, N, K, lda, ldb, ldc, _dt(A), float(alpha), int(split_k), self._tuning_p)
+
+    def gemm_tn(self, A, B, Cm, *, alpha=1.0, split_k=0):
+        args = self._gemm_tn_args(A, B, Cm, alpha, split_k)
+        self._timed("gemm_tn", 2.0 * args[3] * args[4] * args[5], lambda: check(self.lib.lako_gemm_tn(*args, self._stream()), "lako_gemm_tn"))
+
+    def gemm_tn_plan(self, A, B, Cm, *, alpha=1.0, split_k=0):
+        """the launch gemm_tn would make (lako_gemm_tn_plan: the same arguments, nothing launched)"""
+        out = GemmTNPlan()
+        check(self.lib.lako_gemm_tn_plan(*self._gemm_tn_args(A, B, Cm, alpha, split_k), C.byref(out)), "lako_gemm_tn_plan")
+        return out
 
     def gemm_tn_grouped(self, problems, split_k=0, workspace=None):
         """`workspace`: callable(nbytes) → a device uint8 tensor of at least that size (the engine's grow-only scratch), or None.
         [(A [K, M], B [K, N], C [M, N] fp32, alpha[, rows_out]), …] with one K: every C += alpha·Aᵀ·B, one launch per
         TN_GROUP_MAX problems (see lako_gemm_tn_grouped in include/lako_hip.h).  split_k=1: one contributor per output element;
         −1: the same and nothing else adds to C meanwhile (plain read-modify-write); −2: C is overwritten."""
+        for arr, n, K0, dt, flops, ws_p, ws_n in self._gemm_tn_groups(problems, split_k, workspace):
+            self._timed("gemm_tn", flops, lambda: check(self.lib.lako_gemm_tn_grouped(arr, n, K0, dt, int(split_k), self._tuning_p,
+                                                                                      ws_p, ws_n, self._stream()), "lako_gemm_tn_grouped"))
+
+    def gemm_tn_grouped_plan(self, problems, split_k=0, workspace=None):
+        """the launches gemm_tn_grouped would make, one GemmTNPlan per group of TN_GROUP_MAX problems (lako_gemm_tn_grouped_plan: the same
+        item arrays and workspace, nothing launched)"""
+        plans = []
+        for arr, n, K0, dt, _, ws_p, ws_n in self._gemm_tn_groups(problems, split_k, workspace):
+            out = GemmTNPlan()
+            check(self.lib.lako_gemm_tn_grouped_plan(arr, n, K0, dt, int(split_k), self._tuning_p, ws_p, ws_n, C.byref(out)), "lako_gemm_tn_grouped_plan")
+            plans.append(out)
+        return plans
+
+    def _gemm_tn_groups(self, problems, split_k, workspace):
+        """(items, n, K, dtype, flops, workspace pointer, workspace bytes) per group of TN_GROUP_MAX problems"""
         from ._lib import TN_GROUP_MAX, GemmTNItem
         for g0 in range(0, len(problems), TN_GROUP_MAX):
             grp = problems[g0:g0 + TN_GROUP_MAX]
@@ -289,8 +359,7 @@ class HipOps:
                 need = int(self.lib.lako_gemm_tn_grouped_workspace(arr, len(grp), K0, _dt(grp[0][0]), int(split_k), self._tuning_p))
                 if need > 0:
                     ws_p, ws_n = _p(workspace(need)), need
-            self._timed("gemm_tn", flops, lambda: check(self.lib.lako_gemm_tn_grouped(arr, len(grp), K0, _dt(grp[0][0]), int(split_k), self._tuning_p,
-                                                                                      ws_p, ws_n, self._stream()), "lako_gemm_tn_grouped"))
+            yield arr, len(grp), K0, _dt(grp[0][0]), flops, ws_p, ws_n
 
     # ---- norm / embedding / dropout ---------------------------------------------------------------
     def rmsnorm_fwd(self, x, w, y, rstd, eps, drop=None):

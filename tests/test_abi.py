@@ -55,7 +55,7 @@ def test_struct_layouts_match_header_order():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     for cname, py in (("lako_gemm_nt_t", _lib.GemmNT), ("lako_attn_fwd_t", _lib.AttnFwd), ("lako_attn_bwd_t", _lib.AttnBwd),
                       ("lako_dropout_t", _lib.Dropout), ("lako_headbatch_t", _lib.HeadBatch),
-                      ("lako_gemm_tn_item_t", _lib.GemmTNItem)):
+                      ("lako_gemm_tn_item_t", _lib.GemmTNItem), ("lako_gemm_plan_t", _lib.GemmPlan), ("lako_gemm_tn_plan_t", _lib.GemmTNPlan)):
         body = re.search(r"typedef struct \{([^{}]*)\}\s*" + cname, src, re.S).group(1)
         names = []
         for decl in body.split(";"):
@@ -106,6 +106,26 @@ def test_bad_arguments_return_error_codes(lib):
     assert L.lako_pq_scan(x, x, 1000, 8, 16, 256, x, 999, None) == -1                          # ld < n
     assert L.lako_kldiv_bwd(x, x, x, None, 0, 8, None) == -1
     assert L.lako_layernorm_bwd(x, x, None, None, x, x, x, x, None, 16, 2000, 1e-5, 1, None) == -1   # d > the kernel's register budget
+    # the plan queries: null structs, null outputs and the launching calls' own refusals; a valid query fills the plan and launches nothing
+    plan, tnplan = _lib.GemmPlan(), _lib.GemmTNPlan()
+    assert L.lako_gemm_nt_plan(None, ctypes.byref(plan)) == -1 and L.lako_gemm_nt_plan(ctypes.byref(p), None) == -1
+    assert L.lako_gemm_nt_plan(ctypes.byref(p), ctypes.byref(plan)) == -1 and plan.kernel == 0            # M = N = K = 0
+    n = L.lako_last_error(buf, 256)
+    assert n > 0 and b"lako_gemm_nt" in buf.value
+    assert L.lako_gemm_nt_mx_plan(None, x, x, ctypes.byref(plan)) == -1 and L.lako_gemm_nt_mx_plan(ctypes.byref(p), None, None, ctypes.byref(plan)) == -1
+    assert L.lako_gemm_nt_mx_plan(ctypes.byref(p), x, x, None) == -1
+    g = _lib.GemmNT()
+    g.A, g.B, g.C, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, g.in_dtype, g.out_dtype, g.alpha = 4096, 8192, 12288, 128, 768, 768, 768, 768, 768, 1, 1, 1.0
+    assert L.lako_gemm_nt_plan(ctypes.byref(g), ctypes.byref(plan)) == 0 and plan.kernel == _lib.NT_SKINNY and plan.tile_rows == 32
+    g.C = 12288 + 4
+    assert L.lako_gemm_nt_plan(ctypes.byref(g), ctypes.byref(plan)) == -2 and plan.kernel == 0            # C not 8-byte aligned
+    assert L.lako_gemm_tn_plan(None, None, None, 256, 256, 1024, 256, 256, 256, 1, 1.0, 0, None, ctypes.byref(tnplan)) == -1
+    assert L.lako_gemm_tn_plan(x, x, x, 256, 256, 1024, 256, 256, 256, 1, 1.0, 0, None, None) == -1
+    assert L.lako_gemm_tn_plan(x, x, x, 256, 256, 1024, 256, 256, 256, 1, 1.0, 0, None, ctypes.byref(tnplan)) == 0 and tnplan.big == 1
+    assert L.lako_gemm_tn_grouped_plan(None, 1, 1024, 1, 0, None, None, 0, ctypes.byref(tnplan)) == -1
+    items = (_lib.GemmTNItem * 1)()
+    assert L.lako_gemm_tn_grouped_plan(items, 1, 1024, 1, 0, None, None, 0, ctypes.byref(tnplan)) == -1   # null operands / empty problem
+    assert L.lako_gemm_tn_grouped_plan(items, 1, 1024, 1, 0, None, None, 0, None) == -1
 
 
 def test_comm_and_workspace_entry_points_validate_their_arguments(lib):

@@ -258,6 +258,12 @@ def test_fused_gated_epilogues_bit_identical(ops, M, p):
     ops.gemm_nt_four(xn, wi, pre0)
     ops.gated_gelu_fwd(pre0, h0, drop)
     pre1, h1 = torch.full_like(pre0, 7.0), torch.full_like(h0, 7.0)
+    from lako_amd._lib import NT_FOUR, NT_FOUR_GATED
+    old = ops.tuning.nt_variant
+    ops.tuning.nt_variant = 9           # (what gemm_nt_four runs under)
+    assert (ops.gemm_nt_plan(xn, wi, pre0).kernel, ops.gemm_nt_plan(xn, wi, pre0).tile_rows) == (NT_FOUR, 256)
+    ops.tuning.nt_variant = old
+    assert ops.gemm_nt_gated_plan(xn, wi, pre1, h1, drop).kernel == NT_FOUR_GATED
     ops.gemm_nt_gated(xn, wi, pre1, h1, drop)
     assert torch.equal(pre0, pre1) and torch.equal(h0, h1)
     dh = torch.empty(M, f, device=DEV, dtype=torch.bfloat16)
@@ -265,6 +271,7 @@ def test_fused_gated_epilogues_bit_identical(ops, M, p):
     dpre0 = torch.empty_like(pre0)
     ops.gated_gelu_bwd(dh, pre0, dpre0, drop)
     dpre1 = torch.full_like(pre0, 7.0)
+    assert ops.gemm_nt_gated_plan(dy, wo_t, dpre1, pre0, drop, backward=True).kernel == NT_FOUR_GATED
     ops.gemm_nt_gated(dy, wo_t, dpre1, pre0, drop, backward=True)
     assert torch.equal(dpre0, dpre1)
 

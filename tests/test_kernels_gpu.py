@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from lako_amd._lib import (NT_128, NT_EIGHT, NT_EIGHT_256x128, NT_FOUR, NT_MX_EIGHT, NT_MX_FOUR, NT_REFUSED, NT_RING, NT_SKINNY,
+                           NT_SKINNY_NORM)
 from tests.ref_ops import RefOps, keep_mask
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +64,12 @@ def close(got, want, dtype, what, k=1.0, tight=False):
     assert torch.isfinite(got).all(), f"{what}: non-finite output"
 
 
+def bulk(pl):
+    """(kernel, tile rows, ticket queue) of the launch that does the bulk of a planned product: the head of a tail split (always the
+    eight-wave 256-column kernel; the few rows of the tail run on small tiles and are not asserted through this), else the only launch"""
+    return (NT_EIGHT, pl.head_tile, pl.head_queue) if pl.head_rows else (pl.kernel, pl.tile_rows, pl.queue)
+
+
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("M,N,K", [(128, 128, 128), (300, 264, 200), (108, 64, 32), (1024, 768, 768), (77, 2304, 64),
@@ -77,16 +85,27 @@ def test_gemm_nt_plain(ops, ref, dt, M, N, K):
         close(C, Cr, T, f"gemm_nt {dt}->{out_t} {M}x{N}x{K}", tight=True)
 
 
-@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5, 7, 8, 9])
-@pytest.mark.parametrize("M,N,K", [(1024, 768, 768), (700, 520, 200), (256, 256, 32), (2048, 2304, 768), (300, 264, 3072), (128, 768, 72),
-                                   (128, 768, 768), (100, 200, 160), (16, 3072, 768), (130, 776, 3072)])
+TILE_VARIANTS = [0, 1, 2, 3, 4, 5, 7, 8, 9]
+TILE_VARIANT_SHAPES = [(1024, 768, 768), (700, 520, 200), (256, 256, 32), (2048, 2304, 768), (300, 264, 3072), (128, 768, 72),
+                       (128, 768, 768), (100, 200, 160), (16, 3072, 768), (130, 776, 3072)]
+# a variant's OWN kernel (lako_tuning_t.nt_variant): (lako_gemm_plan_t.kernel, tile_rows or None).  tests/test_gemm_plan_cpu.py checks that
+# every variant is planned as its own kernel on at least one of the shapes above with each of the four epilogue classes of the test below —
+# a forced variant that only ever reaches its fallback would leave its kernel unexecuted behind a passing comparison
+TILE_VARIANT_KERNEL = {0: (NT_128, None), 1: (NT_EIGHT_256x128, None), 2: (NT_EIGHT, 256), 3: (NT_FOUR, 192), 4: (NT_RING, None), 5: (NT_SKINNY, 32),
+                       7: (NT_EIGHT, 192), 8: (NT_EIGHT, 288), 9: (NT_FOUR, 256)}
+# the documented fallback of the variants that have one: the four-wave kernels -> the eight-wave 256² kernel, the M <= 256 kernel -> the ring
+TILE_VARIANT_FALLBACK = {3: (NT_EIGHT, 256), 9: (NT_EIGHT, 256), 5: (NT_RING, None)}
+
+
+@pytest.mark.parametrize("variant", TILE_VARIANTS)
+@pytest.mark.parametrize("M,N,K", TILE_VARIANT_SHAPES)
 def test_gemm_nt_tile_variants(ops, ref, variant, M, N, K):
     """every tile variant of the bf16 NT kernel (0: 128², 1: 256×128, 2: 256² 2-buffer, 3 / 9 (round 6): the four-wave kernels with the
     hand-placed K loop, 192- / 256-row tiles — shapes and epilogues they do not take run on variant 2, 4: the 128²
     4-slot ring that skinny problems are dispatched to, 5: the 64² kernel whose four waves split K, for M <= 256 rows — it
     falls back to the ring when K is not a multiple of 32, 7: 192×256 tiles — the 256² kernel's MT = 6 instantiation, whose last
     wave keeps its epilogue scratch behind the K-slice buffers, 8: 288×256 tiles — MT = 9: the last A piece of a K-slice exists for
-    waves 0–3 only, the last epilogue pass is 16 rows; plain epilogues only, the others fall back to 256-row tiles),
+    waves 0–3 only, the last epilogue pass is 16 rows; bf16 in and out),
     persistent and one-tile-per-workgroup grids, ragged edges, fused epilogues."""
     T = torch.bfloat16
     A, B = rnd(M, K, dtype=T, seed=41), rnd(N, K, dtype=T, seed=42)
@@ -98,9 +117,14 @@ def test_gemm_nt_tile_variants(ops, ref, variant, M, N, K):
             ops.set_tuning("gemm_nt_persistent", persistent)
             ops.set_tuning("gemm_nt_wide_epi", wide)
             ops.set_tuning("gemm_nt_group_m", group_m)
-            for kw in (dict(), dict(relu=True, drop=(0.1, 5, 6)), dict(resid=R, drop=(0.1, 7, 8), alpha=0.5), dict(aux=R, aux_scale=1.1)):
+            # (the residual epilogue with and without alpha: the four-wave kernels take it with alpha = 1 only)
+            for kw in (dict(), dict(relu=True, drop=(0.1, 5, 6)), dict(resid=R, drop=(0.1, 7, 8), alpha=0.5), dict(resid=R, drop=(0.1, 7, 8)), dict(aux=R, aux_scale=1.1)):
                 C = torch.empty(M, N, dtype=T, device=dev())
                 Cr = torch.zeros(M, N, device=dev())
+                pl = ops.gemm_nt_plan(A, B, C, **kw)
+                own, fallback = TILE_VARIANT_KERNEL[variant], TILE_VARIANT_FALLBACK.get(variant, TILE_VARIANT_KERNEL[variant])
+                assert (pl.kernel, pl.tile_rows if own[1] else None) == own or (pl.kernel, pl.tile_rows if fallback[1] else None) == fallback, \
+                    f"variant {variant} planned {pl}: neither its own kernel nor its documented fallback"
                 ops.gemm_nt(A, B, C, **kw)
                 ref.gemm_nt(A, B, Cr, **kw)
                 close(C, Cr, T, f"gemm_nt variant {variant} persistent {persistent} wide {wide} group_m {group_m} {list(kw)} {M}x{N}x{K}", tight=True)
@@ -132,6 +156,8 @@ def test_gemm_nt_side_operand_in_lds(ops, ref, M, N, K):
                     ops.set_tuning("gemm_nt_side_lds", side)
                     Cw.fill_(7.0)
                     C = Cw[:, 8:8 + N]
+                    pl = ops.gemm_nt_plan(A, B, C, **kw)
+                    assert (pl.kernel, pl.tile_rows, pl.side_lds) == (NT_EIGHT, {2: 256, 7: 192, 8: 288}[variant], int(side == 1 and N % 8 == 0)), (variant, side, list(kw), pl)
                     ops.gemm_nt(A, B, C, **kw)
                     assert torch.all(Cw[:, :8] == 7.0) and torch.all(Cw[:, 8 + N:] == 7.0), "stores outside the output columns"
                     got[side] = C.clone()
@@ -170,6 +196,9 @@ def test_gemm_nt_eight_phase_equals_two_phase(ops, ref, M, N, K):
                 for pp, glds in ((1, 1), (1, 0), (0, 1)):       # (global_load_lds staging: rows past the edge are clamped, not zero-filled)
                     ops.set_tuning("gemm_nt_pp", pp)
                     ops.set_tuning("gemm_nt_glds", glds)
+                    pl = ops.gemm_nt_plan(A, B, want, **kw)
+                    assert (pl.kernel, pl.tile_rows, pl.eight_phase, pl.wide_epi) == (NT_EIGHT, 256, int(pp == 1 and K >= 128), int(wide == 1 and N % 8 == 0 and kw in (cases[0], cases[1]))), \
+                        (pp, glds, wide, list(kw), pl)
                     for rep in range(3 if M * N * K < 4e10 else 2):
                         C = torch.full((M, N), 7.0, dtype=T, device=dev())
                         ops.gemm_nt(A, B, C, **kw)
@@ -201,12 +230,15 @@ def test_gemm_nt_skinny_tiles(ops, ref, M, N, K):
             for kw in (dict(), dict(relu=True, drop=(0.1, 5, 6)), dict(resid=R, drop=(0.1, 7, 8), alpha=0.5), dict(aux=R, aux_scale=1.1)):
                 C = torch.empty(M, N, dtype=T, device=dev())
                 Cr = torch.zeros(M, N, device=dev())
+                pl = ops.gemm_nt_plan(A, B, C, **kw)
+                assert (pl.kernel, pl.tile_rows) == (NT_SKINNY, {2: 64, 3: 32}[tiles]), (tiles, list(kw), pl)
                 ops.gemm_nt(A, B, C, **kw)
                 ref.gemm_nt(A, B, Cr, **kw)
                 close(C, Cr, T, f"gemm_nt skinny tiles {tiles} {list(kw)} {M}x{N}x{K}", tight=True)
             for kw in (dict(alpha=0.25), dict(resid=Rf)):
                 C = torch.empty(M, N, device=dev())
                 Cr = torch.zeros(M, N, device=dev())
+                assert ops.gemm_nt_plan(A, B, C, **kw).kernel == NT_SKINNY
                 ops.gemm_nt(A, B, C, **kw)
                 ref.gemm_nt(A, B, Cr, **kw)
                 close(C, Cr, T, f"gemm_nt skinny f32 out tiles {tiles} {list(kw)} {M}x{N}x{K}", tight=True)
@@ -253,6 +285,12 @@ def test_gemm_nt_tile_queue(ops, ref):
                 for q in (0, 1, 1):
                     ops.set_tuning("gemm_nt_queue", q)
                     C = torch.empty(M, N, dtype=T, device=dev())
+                    pl = ops.gemm_nt_plan(A, B, C, **kw)
+                    # the queue on the multi-round launches (the 256-row head of a tail split counts), the strided kernels on the other two shapes
+                    if q == 1 and M >= 40000:
+                        assert bulk(pl) == (NT_EIGHT, 256, 1), (M, N, K, list(kw), pl)
+                    else:
+                        assert bulk(pl)[2] == 0, (q, M, N, K, list(kw), pl)
                     ops.gemm_nt(A, B, C, **kw)
                     got.append(C)
                 side = torch.cuda.Stream()
@@ -292,6 +330,8 @@ def test_gemm_nt_norm_fused(ops, ref, M, N, K):
         ops.gemm_nt(xn0, B, C0, **kw)
         C1 = torch.empty(M, N, dtype=T, device=dev())
         xn1, rs1 = torch.full((M, K), 7.0, dtype=T, device=dev()), torch.full((M,), 7.0, device=dev())
+        pl = ops.gemm_nt_plan(A, B, C1, norm=(w, eps, xn1, rs1), **kw)
+        assert (pl.kernel, pl.tile_rows) == ((NT_SKINNY_NORM, 32) if M <= 256 and K <= 1024 else (NT_REFUSED, 0)), (list(kw), pl)
         ops.gemm_nt(A, B, C1, norm=(w, eps, xn1, rs1), **kw)
         torch.testing.assert_close(rs1, rs0, rtol=2e-6, atol=0)
         assert float((xn1.float() - xn0.float()).abs().max()) <= 2.0 ** -7 * float(xn0.float().abs().max())      # one bf16 ulp at most
@@ -317,6 +357,7 @@ def test_gemm_nt_norm_refused_before_any_launch(ops, knobs):
             ops.set_tuning(k_, v_)
         C1 = torch.full((M, N), 7.0, dtype=T, device=dev())
         xn1, rs1 = torch.full((M, K), 7.0, dtype=T, device=dev()), torch.full((M,), 7.0, device=dev())
+        assert ops.gemm_nt_plan(A, B, C1, norm=(w, 1e-6, xn1, rs1)).kernel == NT_REFUSED
         rc = ops._gemm_nt_call(A, B, C1, 1.0, False, None, None, 1.0, None, False, (w, 1e-6, xn1, rs1))
         torch.cuda.synchronize()
         assert rc == -4, rc                                     # LAKO_E_UNSUPPORTED
@@ -351,6 +392,11 @@ def test_gemm_nt_tile_height_plan(ops, ref):
                 ops.set_tuning("gemm_nt_tile288", t288)
                 ops.probe = []
                 C = torch.empty(M, N, dtype=T, device=dev())
+                pl = ops.gemm_nt_plan(A, B, C, **kw)
+                if (t192, t288) == (0, 0):      # 561 tiles of 256 rows: two rounds on the 256² kernel + 51 tiles' rows on a second launch
+                    assert (pl.head_rows, pl.head_tile) == (170 * 256, 256) and pl.kernel in (NT_RING, NT_128), (list(kw), pl)
+                else:                           # 747 tiles of 192 rows in three rounds / 498 of 288 rows in two: one launch
+                    assert (pl.kernel, pl.tile_rows, pl.head_rows) == (NT_EIGHT, 192 if t192 else 288, 0), (t192, t288, list(kw), pl)
                 ops.gemm_nt(A, B, C, **kw)
                 torch.cuda.synchronize()
                 ops.probe = None
@@ -377,8 +423,10 @@ def test_gemm_nt_four_wave_kernels(ops, ref, M, N, K):
     A, B = rnd(M, K, dtype=T, seed=71), rnd(N, K, dtype=T, seed=72)
     R, X = rnd(M, N, dtype=T, seed=73), rnd(M, N, dtype=T, seed=74)
     try:
-        for kw in (dict(), dict(relu=True, drop=(0.1, 5, 6)), dict(drop=(0.1, 9, 10)), dict(alpha=0.5, drop=(0.1, 5, 6)), dict(resid=R, drop=(0.1, 7, 8), alpha=0.5),
-                   dict(resid=R), dict(aux=X, aux_scale=1.1), dict(relu=True, resid=R)):
+        # (alpha alone and residual + dropout with alpha = 1: the two branches of the four-wave epilogue that the alpha = 0.5 cases, which
+        # the eight-wave kernels take, do not reach)
+        for kw in (dict(), dict(alpha=0.5), dict(relu=True, drop=(0.1, 5, 6)), dict(drop=(0.1, 9, 10)), dict(alpha=0.5, drop=(0.1, 5, 6)), dict(resid=R, drop=(0.1, 7, 8), alpha=0.5),
+                   dict(resid=R, drop=(0.1, 7, 8)), dict(resid=R), dict(aux=X, aux_scale=1.1), dict(relu=True, resid=R)):
             got = {}
             # (gemm_nt_four 3: the dropout epilogues through the LDS transposition like the others; 1: straight from the accumulator layout)
             for name, four, variant in (("eight-wave", 0, -1), ("default plan", 1, -1), ("256-row", 1, 9), ("192-row", 1, 3), ("256-row, LDS epilogues", 3, 9),
@@ -386,6 +434,16 @@ def test_gemm_nt_four_wave_kernels(ops, ref, M, N, K):
                 ops.set_tuning("gemm_nt_four", four)
                 ops.set_tuning("gemm_nt_variant", variant)
                 C = torch.full((M, N), float("nan"), dtype=T, device=dev())
+                # the four-wave kernels take alpha alone, {ReLU, dropout}, {residual, dropout} and the aux mask, all but the first with
+                # alpha = 1 (include/lako_hip.h nt_four); the rest — alpha next to dropout or a residual, ReLU + residual — the eight-wave ones
+                takes = not (kw.get("alpha", 1.0) != 1.0 and len(kw) > 1) and not (kw.get("relu") and "resid" in kw)
+                pl = ops.gemm_nt_plan(A, B, C, **kw)
+                if four and takes:          # one launch, at the forced height or (default plan) at either
+                    assert (pl.kernel, pl.head_rows) == (NT_FOUR, 0) and pl.tile_rows in {9: (256,), 3: (192,), -1: (192, 256)}[variant], (name, list(kw), pl)
+                elif variant >= 0:          # a forced four-wave variant hands the call to the eight-wave 256² kernel
+                    assert (pl.kernel, pl.tile_rows, pl.head_rows) == (NT_EIGHT, 256, 0), (name, list(kw), pl)
+                else:                       # the eight-wave plan: 256- or 288-row tiles, with or without a small-tile tail
+                    assert bulk(pl)[0] == NT_EIGHT and bulk(pl)[1] in (256, 288), (name, list(kw), pl)
                 ops.gemm_nt(A, B, C, **kw)
                 torch.cuda.synchronize()
                 got[name] = C
@@ -533,6 +591,14 @@ def test_gemm_tn_four_wave_kernel(ops, ref, K, M, N):
             for four in (0, 1):
                 ops.set_tuning("gemm_tn_four", four)
                 C = C0.clone()
+                pl = ops.gemm_tn_plan(A, B, C, alpha=0.5, split_k=split)
+                # the four-wave kernel takes K ranges of at least 128 rows (lako_tuning_t.tn_four): with one contributor that is every shape
+                # here, 131 rows included; three pieces of 200 or 131 rows are too short and run on the eight-wave kernel
+                # (split_k 3 cuts K into pieces of ceil(K / 3) rounded up to whole 64-row steps: 128 + 72 rows of 200, 64-row pieces of 131)
+                piece = -(-(-(-K // 3)) // 64) * 64 if split == 3 else None
+                long_enough = split != 3 or (piece >= 128 and K - (-(-K // piece) - 1) * piece >= 128)
+                assert (pl.big, pl.four) == (1, int(four and long_enough)), (split, four, pl)
+                assert split != 3 or (pl.split_k, pl.k_chunk) == (-(-K // piece), piece), (split, pl)
                 ops.gemm_tn(A, B, C, alpha=0.5, split_k=split)
                 torch.cuda.synchronize()
                 got.append(C)
@@ -1413,6 +1479,9 @@ def test_gemm_nt_mx_four_wave(ops, ref, M, N, K):
                 ops.set_tuning("gemm_nt_four", four)
                 ops.set_tuning("gemm_nt_variant", variant)
                 C = torch.full((M, N), float("nan"), dtype=T, device=dev())
+                pl = ops.gemm_nt_mx_plan(Aq, As, Bq, Bs, C, **kw)
+                rows = {9: (256,), 3: (192,), -1: (192, 256)}[variant] if four else (256,)
+                assert pl.kernel == (NT_MX_FOUR if four else NT_MX_EIGHT) and pl.tile_rows in rows, (name, list(kw), pl)
                 ops.gemm_nt_mx(Aq, As, Bq, Bs, C, **kw)
                 torch.cuda.synchronize()
                 got[name] = C
