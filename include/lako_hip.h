@@ -210,7 +210,8 @@ int64_t lako_gemm_tn_grouped_workspace(const lako_gemm_tn_item_t* items, int n_i
  * launching call consumes the very plan the query reports) and makes no HIP call of any kind: it runs on a host without a GPU, and
  * no pointer is dereferenced except the host structs.  It returns what the launching call would return before its first launch
  * (LAKO_E_BADARG / _ALIGN / _UNSUPPORTED agree by construction; `out` is then zeroed) and fills `out` on LAKO_OK.  For tests that pin a kernel and
- * for callers that want to know which side of a dispatch gate a shape falls on. */
+ * for callers that want to know which side of a dispatch gate a shape falls on.  The attention has the same queries,
+ * lako_attn_fwd_plan / lako_attn_bwd_plan, declared next to lako_attn_fwd / lako_attn_bwd. */
 enum {
   LAKO_NT_REFUSED = 0,       /* no kernel takes the call */
   LAKO_NT_FOUR = 1,          /* four-wave 256-column tile with the hand-placed K loop, tile_rows 192 | 256 (tuning nt_four) */
@@ -361,6 +362,53 @@ typedef struct {
   const int32_t* order; /* as in lako_attn_fwd_t */
 } lako_attn_bwd_t;
 int lako_attn_bwd(const lako_attn_bwd_t* p, lako_stream_t stream);
+
+/* ---- plan queries (as for the GEMMs above): WHICH attention kernels a call would launch, and with what, without launching ----
+ * Same contract: the arguments of the launching entry point, the same validation and the very plan the launching call consumes, no
+ * HIP call (they run on a host without a GPU), the return value the launching call has before its first launch, `out` zeroed on
+ * refusal.  The forward is one launch; the backward one (the one-pass kernel) or two (dQ pass, then dK/dV pass).  The decision
+ * depends on the environment knobs LAKO_ATTN_PERSIST / LAKO_ATTN_FUSED_NST (read on every call) and LAKO_ATTN_FAST / _FWD_DMA /
+ * _DKV_DMA / _WGS and LAKO_DETERMINISTIC (read once per process). */
+enum {
+  LAKO_ATTN_NONE = 0,
+  LAKO_ATTN_FWD = 1,            /* generic forward (csrc/attn.hip: any dtype, d_head, key count; causal, key mask, score capture) */
+  LAKO_ATTN_BWD_DQ = 2,         /* generic dQ pass (also the bias gradient) */
+  LAKO_ATTN_BWD_DKV = 3,        /* generic dK/dV pass */
+  LAKO_ATTN_ENC_FWD = 4,        /* encoder fast path (csrc/attn_enc.hip), one workgroup per (sequence, head, query range): register staging */
+  LAKO_ATTN_ENC_FWD_C = 5,      /* ... K / V by LDS-DMA (the default forward) */
+  LAKO_ATTN_ENC_FWD_P = 6,      /* persistent forward: one 16-wave workgroup per CU walking the sequences of a head */
+  LAKO_ATTN_ENC_BWD_DQ = 7,     /* dQ pass, several batch rows per workgroup */
+  LAKO_ATTN_ENC_BWD_DQ_P = 8,   /* persistent dQ pass */
+  LAKO_ATTN_ENC_BWD_DKV = 9,    /* dK/dV pass per (sequence, head, key range); dma_stage tells how its images arrive */
+  LAKO_ATTN_ENC_BWD_DKV_P = 10, /* persistent dK/dV pass */
+  LAKO_ATTN_ENC_BWD_FUSED = 11  /* one-pass backward (<= 224 key rows) */
+};
+typedef struct {
+  int32_t kernel;    /* LAKO_ATTN_* */
+  /* which instantiation / form of it */
+  int32_t drop;      /* fast path: the dropout instantiation */
+  int32_t capture;   /* LAKO_ATTN_FWD: the score-capture instantiation */
+  int32_t ring;      /* LAKO_ATTN_ENC_BWD_FUSED: stages of the slab ring, 3 | 4 */
+  int32_t dma_stage; /* LAKO_ATTN_ENC_BWD_DKV: 1 = LDS images by LDS-DMA, 0 = register staging */
+  /* the launch */
+  int32_t gx, gy, gz; /* grid, in workgroups */
+  int32_t block;      /* threads per workgroup */
+  int32_t lds;        /* dynamic LDS bytes */
+  /* what the kernel is told beyond the caller's arguments */
+  int32_t chunk_rows;    /* LDS-side rows per chunk (multiple of 32, <= 256) */
+  int32_t blocks_per_wg; /* register-side 16-row blocks per workgroup */
+  int32_t bn_per_wg;     /* dQ passes: batch rows walked by one workgroup */
+  int32_t rq, rk;        /* one-pass backward, padded layout: rows per sequence of the q / k side */
+  int32_t grid_x, grid_z; /* LAKO_ATTN_BWD_DQ, grid_x > 0: gx is a 1-D XCD-grouped grid standing for (grid_x, H, grid_z) */
+  int32_t R, rel_off;    /* bias table extent and offset the kernel indexes with (fast path without a table: Lq + Lk - 1, Lq - 1) */
+  int32_t drel;          /* 1: the launch adds to the caller's bias gradient */
+} lako_attn_launch_t;
+typedef struct {
+  int32_t n_launches; /* 1 | 2 */
+  lako_attn_launch_t launch[2];
+} lako_attn_plan_t;
+int lako_attn_fwd_plan(const lako_attn_fwd_t* p, lako_attn_plan_t* out);
+int lako_attn_bwd_plan(const lako_attn_bwd_t* p, lako_attn_plan_t* out);
 
 /* ---- cross-attention in the encoder-state space (the decoder's EncDecAttention over the concatenated n_passages·L encoder
  * states, src/model.py:286-349 / HF5:281-369; bf16, d_kv 64, ragged keys) --------------------------------------------------

@@ -102,6 +102,36 @@ class AttnBwd(C.Structure):
                 ("dtype", i32), ("drop", Dropout), ("q_off", vp), ("k_off", vp), ("order", vp)]
 
 
+class AttnLaunch(C.Structure):
+    """lako_attn_launch_t: one launch of an attention plan"""
+    _fields_ = [(n, i32) for n in ("kernel", "drop", "capture", "ring", "dma_stage", "gx", "gy", "gz", "block", "lds", "chunk_rows",
+                                   "blocks_per_wg", "bn_per_wg", "rq", "rk", "grid_x", "grid_z", "R", "rel_off", "drel")]
+
+    def __repr__(self):
+        return "AttnLaunch(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_ if getattr(self, n) or n == "kernel") + ")"
+
+
+class AttnPlan(C.Structure):
+    """lako_attn_plan_t: what lako_attn_fwd_plan / lako_attn_bwd_plan say the launching call would run"""
+    _fields_ = [("n_launches", i32), ("launch", AttnLaunch * 2)]
+
+    @property
+    def launches(self):
+        return [self.launch[i] for i in range(self.n_launches)]
+
+    @property
+    def kernels(self):
+        return [l.kernel for l in self.launches]
+
+    def __repr__(self):
+        return f"AttnPlan({self.launches})"
+
+
+# lako_attn_launch_t.kernel (include/lako_hip.h LAKO_ATTN_*)
+(ATTN_NONE, ATTN_FWD, ATTN_BWD_DQ, ATTN_BWD_DKV, ATTN_ENC_FWD, ATTN_ENC_FWD_C, ATTN_ENC_FWD_P, ATTN_ENC_BWD_DQ, ATTN_ENC_BWD_DQ_P,
+ ATTN_ENC_BWD_DKV, ATTN_ENC_BWD_DKV_P, ATTN_ENC_BWD_FUSED) = range(12)
+
+
 # name -> argtypes (restype is always int).  Must list EVERY function include/lako_hip.h declares:
 # tests/test_abi.py cross-checks this table against the header and the .so's dynamic symbols.
 SIGNATURES = {
@@ -137,6 +167,8 @@ SIGNATURES = {
     "lako_relpos_reduce": [vp, vp, vp, i32, i32, i32, vp],
     "lako_attn_fwd": [C.POINTER(AttnFwd), vp],
     "lako_attn_bwd": [C.POINTER(AttnBwd), vp],
+    "lako_attn_fwd_plan": [C.POINTER(AttnFwd), C.POINTER(AttnPlan)],
+    "lako_attn_bwd_plan": [C.POINTER(AttnBwd), C.POINTER(AttnPlan)],
     "lako_xattn_scores": [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, vp],
     "lako_xattn_context": [vp, i64, vp, i64, vp, vp, vp, i64, i64, i64, i32, i32, i32, i32, vp],
     "lako_xattn_softmax_fwd": [vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, i32, Dropout, vp],

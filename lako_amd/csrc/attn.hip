@@ -837,218 +837,225 @@ int pick_chunk(int L, int R, bool merge) {
   return ch;
 }
 
-// raise the kernel's dynamic-LDS limit only when a launch needs more than any earlier one ON THIS DEVICE (`cur` is a per-instantiation
-// static owned by the caller; the attribute is per device: common.h)
-template <typename K>
-void set_lds_attr(K kern, int bytes, lako_lds_cur_t& cur) {
-  lako_raise_max_lds(reinterpret_cast<const void*>(kern), bytes, cur);
-}
-
-// choose register-side blocks per workgroup: all of them when there are already plenty of workgroups,
-// otherwise split so the grid reaches ~1024 workgroups (no LDS-side merge needed: blocks are independent)
-inline int pick_blocks_per_wg(int nblocks, int64_t bh) {
-  int64_t want = 1024;
-  if (bh >= want || nblocks <= 4) return ((nblocks + 3) / 4) * 4;
-  int groups = (int)((want + bh - 1) / bh);
-  int per = (nblocks + groups - 1) / groups;
-  per = ((per + 3) / 4) * 4;
-  return per < 4 ? 4 : per;
+// f(AC<T, DK>{}) for the element type and head size of a call (check_common has refused every other)
+template <typename F>
+auto attn_typed(int dtype, int d_head, F&& f) {
+  if (dtype == LAKO_BF16) return d_head == 64 ? f(AC<bf16_t, 64>{}) : d_head == 128 ? f(AC<bf16_t, 128>{}) : f(AC<bf16_t, 32>{});
+  return d_head == 64 ? f(AC<float, 64>{}) : d_head == 128 ? f(AC<float, 128>{}) : f(AC<float, 32>{});
 }
 
 template <typename T, int DK>
-int run_fwd(AttnArgs& a, hipStream_t s) {
+void gen_fwd_plan(const AttnArgs& a, AttnPlan& pl) {
   const int nqb = (a.Lq + 15) / 16;
-  a.chunk_rows = pick_chunk<T, DK, false>(a.Lk, a.R, nqb == 1);
-  a.blocks_per_wg = pick_blocks_per_wg(nqb, (int64_t)a.Bn * a.H);
-  const int lds = lds_bytes_fwd<T, DK>(a.chunk_rows, a.R, nqb == 1);
-  dim3 grid((nqb + a.blocks_per_wg - 1) / a.blocks_per_wg, a.H, a.Bn);
-  if (a.scores_out) {
-    static lako_lds_cur_t curc;
-    set_lds_attr(&attn_fwd_kernel<T, DK, true>, lds, curc);
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DK, true>), grid, dim3(256), lds, s, a);
-  } else {
-    static lako_lds_cur_t cur;
-    set_lds_attr(&attn_fwd_kernel<T, DK, false>, lds, cur);
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DK, false>), grid, dim3(256), lds, s, a);
-  }
-  return 0;
+  AttnLaunch& l = attn_plan_add(pl, a, LAKO_ATTN_FWD, 256);
+  l.capture = a.scores_out != nullptr;
+  l.chunk_rows = pick_chunk<T, DK, false>(a.Lk, a.R, nqb == 1);
+  l.blocks_per_wg = blocks_per_wg(nqb, (int64_t)a.Bn * a.H, 4);
+  l.lds = lds_bytes_fwd<T, DK>(l.chunk_rows, a.R, nqb == 1);
+  l.gx = (nqb + l.blocks_per_wg - 1) / l.blocks_per_wg, l.gy = a.H, l.gz = a.Bn;
 }
 
 template <typename T, int DK>
-int run_bwd(AttnArgs& a, hipStream_t s) {
+void gen_bwd_plan(const AttnArgs& a, const AttnKnobs& kn, AttnPlan& pl) {
   {  // dQ pass
-    AttnArgs q = a;
     const int nqb = (a.Lq + 15) / 16;
+    AttnLaunch& q = attn_plan_add(pl, a, LAKO_ATTN_BWD_DQ, 256);
     q.chunk_rows = pick_chunk<T, DK, true>(a.Lk, a.R, nqb == 1);
-    q.blocks_per_wg = pick_blocks_per_wg(nqb, (int64_t)a.Bn * a.H);
+    // The kernel's key-split mode (one query block over more than 64 keys: the four waves share the block and split the keys) does not
+    // combine with its register accumulation of the bias gradient (all keys in one chunk: each wave reduces the diagonals of ITS OWN query
+    // block, so only wave 0's share of the keys would reach the table).  Two chunks keep the kernel on the LDS atomics every wave issues.
+    if (a.drel && nqb == 1 && a.Lk > 64 && a.Lk <= q.chunk_rows) q.chunk_rows -= 32;
+    q.blocks_per_wg = blocks_per_wg(nqb, (int64_t)a.Bn * a.H, 4);
     q.bn_per_wg = 1;
-#ifdef LAKO_EXPERIMENTS   // timing experiments (bits 4 / 8 drop the bias-gradient flushes: wrong results) — never in the release library
-    static const int dbg = getenv("LAKO_ATTN_DEBUG") ? atoi(getenv("LAKO_ATTN_DEBUG")) : 0;
-#else
-    constexpr int dbg = 0;
-#endif
-    if ((a.drel || (dbg & 1)) && a.Lk <= q.chunk_rows) {
+    if ((a.drel || ATTN_DBG(kn, 1)) && a.Lk <= q.chunk_rows) {
       // bias gradient: one query block per wave, several batch rows per workgroup (register accumulation of dS)
       q.blocks_per_wg = 4;
-      const int64_t wgs = (int64_t)a.Bn * a.H * ((nqb + 3) / 4);
-      static const int wg_target = getenv("LAKO_ATTN_WGS") ? atoi(getenv("LAKO_ATTN_WGS")) : 1024;
-      q.bn_per_wg = (int)(wgs / wg_target > 1 ? wgs / wg_target : 1);
-      if (q.bn_per_wg > OFFS_MAX - 1) q.bn_per_wg = OFFS_MAX - 1;   // the kernel stages bn_per_wg + 1 row offsets in LDS
+      q.bn_per_wg = attn_bn_per_wg((int64_t)a.Bn * a.H * ((nqb + 3) / 4), kn);
     }
-    const int lds = lds_bytes_bwd<T, DK>(q.chunk_rows, a.R, nqb == 1);
-    static lako_lds_cur_t cur0;
-    set_lds_attr(&attn_bwd_kernel<T, DK, 0>, lds, cur0);
-    dim3 grid((nqb + q.blocks_per_wg - 1) / q.blocks_per_wg, a.H, (a.Bn + q.bn_per_wg - 1) / q.bn_per_wg);
-    q.grid_x = 0;
-    q.dbg_flags = dbg;
-    if (grid.x > 1 && !(dbg & 2)) {
-      q.grid_x = (int)grid.x;
-      q.grid_z = (int)grid.z;
-      const int groups = (int)(grid.y * grid.z);
-      grid = dim3((unsigned)(((groups + 7) / 8) * 8 * q.grid_x), 1, 1);
+    q.lds = lds_bytes_bwd<T, DK>(q.chunk_rows, a.R, nqb == 1);
+    q.gx = (nqb + q.blocks_per_wg - 1) / q.blocks_per_wg, q.gy = a.H, q.gz = (a.Bn + q.bn_per_wg - 1) / q.bn_per_wg;
+    if (q.gx > 1 && !ATTN_DBG(kn, 2)) {
+      q.grid_x = q.gx;
+      q.grid_z = q.gz;
+      const int groups = q.gy * q.gz;
+      q.gx = ((groups + 7) / 8) * 8 * q.grid_x, q.gy = 1, q.gz = 1;
     }
-    hipLaunchKernelGGL((attn_bwd_kernel<T, DK, 0>), grid, dim3(256), lds, s, q);
   }
   {  // dK/dV pass
-    AttnArgs k = a;
-    k.bn_per_wg = 1;
-    k.grid_x = 0;
-    k.chunk_rows = pick_chunk<T, DK, true>(a.Lq, a.R, false);
     const int nkb = (a.Lk + 15) / 16;
-    k.blocks_per_wg = pick_blocks_per_wg(nkb, (int64_t)a.Bn * a.H);
-    const int lds = lds_bytes_bwd<T, DK>(k.chunk_rows, a.R, false);
-    static lako_lds_cur_t cur1;
-    set_lds_attr(&attn_bwd_kernel<T, DK, 1>, lds, cur1);
-    dim3 grid((nkb + k.blocks_per_wg - 1) / k.blocks_per_wg, a.H, a.Bn);
-    hipLaunchKernelGGL((attn_bwd_kernel<T, DK, 1>), grid, dim3(256), lds, s, k);
+    AttnLaunch& k = attn_plan_add(pl, a, LAKO_ATTN_BWD_DKV, 256);
+    k.bn_per_wg = 1;
+    k.chunk_rows = pick_chunk<T, DK, true>(a.Lq, a.R, false);
+    k.blocks_per_wg = blocks_per_wg(nkb, (int64_t)a.Bn * a.H, 4);
+    k.lds = lds_bytes_bwd<T, DK>(k.chunk_rows, a.R, false);
+    k.gx = (nkb + k.blocks_per_wg - 1) / k.blocks_per_wg, k.gy = a.H, k.gz = a.Bn;
   }
-  return 0;
 }
 
-int check_common(const char* fn, int Bn, int H, int Lq, int Lk, int d_head, int dtype, int64_t qst, int64_t kst,
-                 int64_t vst, int64_t ost, const void* rel_bias, int R, float p) {
-  if (!(Bn > 0 && H > 0 && Lq > 0 && Lk > 0)) { lako_set_error("%s: bad dims", fn); return LAKO_E_BADARG; }
-  if (!(Bn < 65536 && H < 65536)) { lako_set_error("%s: Bn/H too large for the grid", fn); return LAKO_E_BADARG; }
-  if (!(dtype == LAKO_F32 || dtype == LAKO_BF16)) { lako_set_error("%s: bad dtype", fn); return LAKO_E_BADARG; }
-  if (!(d_head == 32 || d_head == 64 || d_head == 128)) {
-    lako_set_error("%s: d_head=%d unsupported (32, 64 or 128)", fn, d_head);
+// ---- the decision: pure functions of (arguments, dtype, d_head, knobs) ----------------------------------------------------------
+AttnPlan attn_fwd_plan(const AttnArgs& a, int dtype, int d_head, const AttnKnobs& kn) {
+  AttnPlan pl{};
+  if (attn_enc_supported(a, dtype, d_head, kn)) attn_enc_fwd_plan(a, kn, pl);
+  else attn_typed(dtype, d_head, [&](auto c) { gen_fwd_plan<typename decltype(c)::Elem, decltype(c)::DHEAD>(a, pl); });
+  return pl;
+}
+
+AttnPlan attn_bwd_plan(const AttnArgs& a, int dtype, int d_head, const AttnKnobs& kn) {
+  AttnPlan pl{};
+  const bool enc = attn_enc_supported(a, dtype, d_head, kn);
+  if (enc && attn_enc_fused_fits(a, kn)) attn_enc_fused_plan(a, kn, pl);
+  // LAKO_DETERMINISTIC: the fast path's two-pass kernels add into the workgroup's bias-gradient table by LDS float atomics in arrival
+  // order — not taken in that mode: the generic kernels, whose contributions go through det.h
+  else if (enc && !kn.det) attn_enc_two_pass_plan(a, kn, pl);
+  else attn_typed(dtype, d_head, [&](auto c) { gen_bwd_plan<typename decltype(c)::Elem, decltype(c)::DHEAD>(a, kn, pl); });
+  return pl;
+}
+
+// ---- the launch: run a plan ---------------------------------------------------------------------------------------------------------
+template <typename T, int DK>
+void gen_launch(const AttnLaunch& l, AttnArgs x, const AttnKnobs& kn, hipStream_t s) {
+  switch (l.kernel) {
+    case LAKO_ATTN_FWD:
+      return l.capture ? attn_launch<&attn_fwd_kernel<T, DK, true>>(l, x, s) : attn_launch<&attn_fwd_kernel<T, DK, false>>(l, x, s);
+    case LAKO_ATTN_BWD_DQ:
+      x.dbg_flags = ATTN_DBG(kn, -1);
+      return attn_launch<&attn_bwd_kernel<T, DK, 0>>(l, x, s);
+    default:
+      return attn_launch<&attn_bwd_kernel<T, DK, 1>>(l, x, s);
+  }
+}
+
+void attn_run(const AttnPlan& pl, const AttnArgs& a, int dtype, int d_head, const AttnKnobs& kn, hipStream_t s) {
+  for (int i = 0; i < pl.n_launches; ++i) {
+    const AttnLaunch& l = pl.launch[i];
+    const AttnArgs x = attn_launch_args(a, l);
+    if (l.kernel >= LAKO_ATTN_ENC_FWD) attn_enc_launch(l, x, kn, s);
+    else attn_typed(dtype, d_head, [&](auto c) { gen_launch<typename decltype(c)::Elem, decltype(c)::DHEAD>(l, x, kn, s); });
+  }
+}
+
+template <typename P>   // lako_attn_fwd_t | lako_attn_bwd_t
+int check_common(const char* fn, const P& p) {
+  if (!(p.Bn > 0 && p.H > 0 && p.Lq > 0 && p.Lk > 0)) { lako_set_error("%s: bad dims", fn); return LAKO_E_BADARG; }
+  if (!(p.Bn < 65536 && p.H < 65536)) { lako_set_error("%s: Bn/H too large for the grid", fn); return LAKO_E_BADARG; }
+  if (!(p.dtype == LAKO_F32 || p.dtype == LAKO_BF16)) { lako_set_error("%s: bad dtype", fn); return LAKO_E_BADARG; }
+  if (!(p.d_head == 32 || p.d_head == 64 || p.d_head == 128)) {
+    lako_set_error("%s: d_head=%d unsupported (32, 64 or 128)", fn, p.d_head);
     return LAKO_E_UNSUPPORTED;
   }
-  const int esz = dtype == LAKO_F32 ? 4 : 2;
-  if ((qst * esz) % 16 || (kst * esz) % 16 || (vst * esz) % 16 || (ost * esz) % 16) {
+  const int esz = p.dtype == LAKO_F32 ? 4 : 2;
+  if ((p.q_stride_t * esz) % 16 || (p.k_stride_t * esz) % 16 || (p.v_stride_t * esz) % 16 || (p.o_stride_t * esz) % 16) {
     lako_set_error("%s: token strides must be multiples of 16 bytes", fn);
     return LAKO_E_ALIGN;
   }
-  if (rel_bias && !(R > 0 && R <= 4096)) { lako_set_error("%s: bad R=%d", fn, R); return LAKO_E_BADARG; }
-  if (!(p >= 0.f && p < 1.f)) { lako_set_error("%s: dropout p out of range", fn); return LAKO_E_BADARG; }
-  if (p > 0.f && (int64_t)Bn * H * ((Lq + 3) / 4) * ((Lk + 3) / 4) >= (1ll << 32)) {
+  if (p.rel_bias && !(p.R > 0 && p.R <= 4096)) { lako_set_error("%s: bad R=%d", fn, p.R); return LAKO_E_BADARG; }
+  if (!(p.drop.p >= 0.f && p.drop.p < 1.f)) { lako_set_error("%s: dropout p out of range", fn); return LAKO_E_BADARG; }
+  if (p.drop.p > 0.f && (int64_t)p.Bn * p.H * ((p.Lq + 3) / 4) * ((p.Lk + 3) / 4) >= (1ll << 32)) {
     lako_set_error("%s: dropout block index exceeds 32 bits", fn);
     return LAKO_E_UNSUPPORTED;
   }
   return LAKO_OK;
 }
 
-void set_drop(AttnArgs& a, const lako_dropout_t& d) {
+// the AttnArgs fields the forward and the backward structs have in common (the tensors are the caller's to set)
+template <typename P>
+AttnArgs attn_args_from(const P& p, const AttnKnobs& kn) {
+  AttnArgs a = {};
+  a.q = (const char*)p.q; a.k = (const char*)p.k; a.v = (const char*)p.v;
+  a.stats = p.lse;
+  a.rel_bias = p.rel_bias;
+  a.key_mask = p.key_mask;
+  a.qsb = p.q_stride_b; a.qst = p.q_stride_t; a.ksb = p.k_stride_b; a.kst = p.k_stride_t;
+  a.vsb = p.v_stride_b; a.vst = p.v_stride_t; a.osb = p.o_stride_b; a.ost = p.o_stride_t;
+  a.R = p.rel_bias ? p.R : 0;
+  a.rel_off = p.rel_off;
+  a.causal = p.causal;
+  a.causal_off = p.causal_off;
+  a.Bn = p.Bn; a.H = p.H; a.Lq = p.Lq; a.Lk = p.Lk;
+  a.q_off = p.q_off; a.k_off = p.k_off; a.order = p.order;
   a.drop_t16 = 0;
   a.drop_scale = 1.0f;
-  if (d.p > 0.f) {
-    uint32_t t = (uint32_t)((double)d.p * 65536.0 + 0.5);
+  if (p.drop.p > 0.f) {
+    uint32_t t = (uint32_t)((double)p.drop.p * 65536.0 + 0.5);
     a.drop_t16 = t < 1 ? 1 : (t > 65535 ? 65535 : t);
-    a.drop_scale = 1.0f / (1.0f - d.p);
+    a.drop_scale = 1.0f / (1.0f - p.drop.p);
   }
-  a.drop_key = lako_drop_key(d.seed, d.site);
-  a.det = lako_det::on() ? 1 : 0;
+  a.drop_key = lako_drop_key(p.drop.seed, p.drop.site);
+  a.det = kn.det ? 1 : 0;
+  return a;
 }
 
-}  // namespace
-
-#define ATTN_DISPATCH(dtype, dhead, FN, args, s)                    \
-  if ((dtype) == LAKO_BF16) {                                       \
-    if ((dhead) == 64) FN<bf16_t, 64>(args, s);                     \
-    else if ((dhead) == 128) FN<bf16_t, 128>(args, s);              \
-    else FN<bf16_t, 32>(args, s);                                   \
-  } else {                                                          \
-    if ((dhead) == 64) FN<float, 64>(args, s);                      \
-    else if ((dhead) == 128) FN<float, 128>(args, s);               \
-    else FN<float, 32>(args, s);                                    \
-  }
-
-extern "C" int lako_attn_fwd(const lako_attn_fwd_t* p, lako_stream_t stream) {
-  LAKO_CHECK_ARG(p != nullptr, "lako_attn_fwd: null params");
-  int rc = check_common("lako_attn_fwd", p->Bn, p->H, p->Lq, p->Lk, p->d_head, p->dtype, p->q_stride_t, p->k_stride_t,
-                        p->v_stride_t, p->o_stride_t, p->rel_bias, p->R, p->drop.p);
-  if (rc) return rc;
+// Validation, then the plan: everything lako_attn_fwd / lako_attn_bwd do before their first launch, shared with the plan queries (the
+// messages name the launching entry point).  A refusal leaves the plan zeroed, and nothing is in flight.
+int attn_fwd_decide(const lako_attn_fwd_t* p, const AttnKnobs& kn, AttnArgs& a, AttnPlan& pl) {
+  const char* fn = "lako_attn_fwd";
+  pl = AttnPlan{};
+  LAKO_CHECK_ARG(p != nullptr, "%s: null params", fn);
+  if (const int rc = check_common(fn, *p)) return rc;
   LAKO_CHECK_ALIGN(p->q, 16);
   LAKO_CHECK_ALIGN(p->k, 16);
   LAKO_CHECK_ALIGN(p->v, 16);
   LAKO_CHECK_ALIGN(p->out, 8);
-  AttnArgs a = {};
-  a.q = (const char*)p->q;
-  a.k = (const char*)p->k;
-  a.v = (const char*)p->v;
+  a = attn_args_from(*p, kn);
   a.out = (char*)p->out;
-  a.stats = p->lse;
-  a.rel_bias = p->rel_bias;
-  a.key_mask = p->key_mask;
   a.scores_out = p->scores_out;
-  a.qsb = p->q_stride_b; a.qst = p->q_stride_t; a.ksb = p->k_stride_b; a.kst = p->k_stride_t;
-  a.vsb = p->v_stride_b; a.vst = p->v_stride_t; a.osb = p->o_stride_b; a.ost = p->o_stride_t;
-  a.R = p->rel_bias ? p->R : 0;
-  a.rel_off = p->rel_off;
-  a.causal = p->causal;
-  a.causal_off = p->causal_off;
-  a.Bn = p->Bn; a.H = p->H; a.Lq = p->Lq; a.Lk = p->Lk;
-  a.q_off = p->q_off;
-  a.k_off = p->k_off;
-  a.order = p->order;
-  LAKO_CHECK_ARG(!(p->scores_out && (p->q_off || p->k_off)), "lako_attn_fwd: score capture needs the padded layout");
-  LAKO_CHECK_ARG(!(p->key_mask && p->k_off), "lako_attn_fwd: ragged keys carry no padding — pass key_mask = NULL");
-  set_drop(a, p->drop);
-  if (lako_attn_enc_supported(a, p->dtype, p->d_head)) lako_attn_enc_fwd(a, (hipStream_t)stream);
-  else ATTN_DISPATCH(p->dtype, p->d_head, run_fwd, a, (hipStream_t)stream);
+  LAKO_CHECK_ARG(!(p->scores_out && (p->q_off || p->k_off)), "%s: score capture needs the padded layout", fn);
+  LAKO_CHECK_ARG(!(p->key_mask && p->k_off), "%s: ragged keys carry no padding — pass key_mask = NULL", fn);
+  pl = attn_fwd_plan(a, p->dtype, p->d_head, kn);
+  return LAKO_OK;
+}
+
+int attn_bwd_decide(const lako_attn_bwd_t* p, const AttnKnobs& kn, AttnArgs& a, AttnPlan& pl) {
+  const char* fn = "lako_attn_bwd";
+  pl = AttnPlan{};
+  LAKO_CHECK_ARG(p != nullptr, "%s: null params", fn);
+  if (const int rc = check_common(fn, *p)) return rc;
+  LAKO_CHECK_ARG(p->lse && p->out && p->dout && p->dq_out && p->dk_out && p->dv_out, "%s: null tensor", fn);
+  LAKO_CHECK_ARG(!p->drel || p->rel_bias, "%s: drel without rel_bias", fn);
+  a = attn_args_from(*p, kn);
+  a.o = (const char*)p->out; a.dout = (const char*)p->dout;
+  a.dq = (char*)p->dq_out; a.dk = (char*)p->dk_out; a.dv = (char*)p->dv_out;
+  a.drel = p->drel;
+  LAKO_CHECK_ARG(!(p->key_mask && p->k_off), "%s: ragged keys carry no padding — pass key_mask = NULL", fn);
+  if (a.det && a.drel && (int64_t)a.H * a.R > lako_det::SLOTS) {
+    lako_set_error("%s: LAKO_DETERMINISTIC holds the bias gradient of %d heads x %d offsets in a table of %d slots", fn, a.H, a.R, lako_det::SLOTS);
+    return LAKO_E_UNSUPPORTED;
+  }
+  pl = attn_bwd_plan(a, p->dtype, p->d_head, kn);
+  return LAKO_OK;
+}
+
+}  // namespace
+
+extern "C" int lako_attn_fwd(const lako_attn_fwd_t* p, lako_stream_t stream) {
+  const AttnKnobs kn = attn_knobs();
+  AttnArgs a;
+  AttnPlan pl;
+  if (const int rc = attn_fwd_decide(p, kn, a, pl)) return rc;
+  attn_run(pl, a, p->dtype, p->d_head, kn, (hipStream_t)stream);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }
 
 extern "C" int lako_attn_bwd(const lako_attn_bwd_t* p, lako_stream_t stream) {
-  LAKO_CHECK_ARG(p != nullptr, "lako_attn_bwd: null params");
-  int rc = check_common("lako_attn_bwd", p->Bn, p->H, p->Lq, p->Lk, p->d_head, p->dtype, p->q_stride_t, p->k_stride_t,
-                        p->v_stride_t, p->o_stride_t, p->rel_bias, p->R, p->drop.p);
-  if (rc) return rc;
-  LAKO_CHECK_ARG(p->lse && p->out && p->dout && p->dq_out && p->dk_out && p->dv_out, "lako_attn_bwd: null tensor");
-  LAKO_CHECK_ARG(!p->drel || p->rel_bias, "lako_attn_bwd: drel without rel_bias");
-  AttnArgs a = {};
-  a.q = (const char*)p->q;
-  a.k = (const char*)p->k;
-  a.v = (const char*)p->v;
-  a.o = (const char*)p->out;
-  a.dout = (const char*)p->dout;
-  a.dq = (char*)p->dq_out;
-  a.dk = (char*)p->dk_out;
-  a.dv = (char*)p->dv_out;
-  a.stats = p->lse;
-  a.rel_bias = p->rel_bias;
-  a.drel = p->drel;
-  a.key_mask = p->key_mask;
-  a.qsb = p->q_stride_b; a.qst = p->q_stride_t; a.ksb = p->k_stride_b; a.kst = p->k_stride_t;
-  a.vsb = p->v_stride_b; a.vst = p->v_stride_t; a.osb = p->o_stride_b; a.ost = p->o_stride_t;
-  a.R = p->rel_bias ? p->R : 0;
-  a.rel_off = p->rel_off;
-  a.causal = p->causal;
-  a.causal_off = p->causal_off;
-  a.Bn = p->Bn; a.H = p->H; a.Lq = p->Lq; a.Lk = p->Lk;
-  a.q_off = p->q_off;
-  a.k_off = p->k_off;
-  a.order = p->order;
-  LAKO_CHECK_ARG(!(p->key_mask && p->k_off), "lako_attn_bwd: ragged keys carry no padding — pass key_mask = NULL");
-  set_drop(a, p->drop);
-  if (a.det && a.drel && (int64_t)a.H * a.R > lako_det::SLOTS) {
-    lako_set_error("lako_attn_bwd: LAKO_DETERMINISTIC holds the bias gradient of %d heads x %d offsets in a table of %d slots", a.H, a.R, lako_det::SLOTS);
-    return LAKO_E_UNSUPPORTED;
-  }
-  bool done = false;      // (the encoder's fast path declines in LAKO_DETERMINISTIC mode where its one-pass kernel does not apply)
-  if (lako_attn_enc_supported(a, p->dtype, p->d_head)) done = lako_attn_enc_bwd(a, (hipStream_t)stream) == 0;
-  if (!done) ATTN_DISPATCH(p->dtype, p->d_head, run_bwd, a, (hipStream_t)stream);
+  const AttnKnobs kn = attn_knobs();
+  AttnArgs a;
+  AttnPlan pl;
+  if (const int rc = attn_bwd_decide(p, kn, a, pl)) return rc;
+  attn_run(pl, a, p->dtype, p->d_head, kn, (hipStream_t)stream);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
+}
+
+// the plan queries: the same decision, nothing launched, no HIP call
+extern "C" int lako_attn_fwd_plan(const lako_attn_fwd_t* p, lako_attn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_attn_fwd_plan: null out");
+  AttnArgs a;
+  return attn_fwd_decide(p, attn_knobs(), a, *out);
+}
+
+extern "C" int lako_attn_bwd_plan(const lako_attn_bwd_t* p, lako_attn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_attn_bwd_plan: null out");
+  AttnArgs a;
+  return attn_bwd_decide(p, attn_knobs(), a, *out);
 }

@@ -1811,28 +1811,6 @@ __global__ __launch_bounds__(FB_NW * 64) void enc_bwd_fused_kernel(AttnArgs a) {
   FB_STAMP_AT(255, 3);
 }
 
-template <typename K>
-void eset_lds(K kern, int bytes, lako_lds_cur_t& cur) {
-  lako_raise_max_lds(reinterpret_cast<const void*>(kern), bytes, cur);
-}
-
-// query / key blocks per workgroup: all of them when there are already plenty of workgroups, otherwise split so that the grid
-// reaches ~1024 workgroups (multiples of the workgroup's wave count)
-inline int eblocks_per_wg(int nblocks, int64_t bh, int nw) {
-  const int64_t want = 1024;
-  if (bh >= want || nblocks <= nw) return ((nblocks + nw - 1) / nw) * nw;
-  const int groups = (int)((want + bh - 1) / bh);
-  int per = (nblocks + groups - 1) / groups;
-  per = ((per + nw - 1) / nw) * nw;
-  return per < nw ? nw : per;
-}
-
-#define EDISPATCH(KERN, NTHR, drop, grid, lds, s, args)                                                                          \
-  do {                                                                                                                           \
-    if (drop) { static lako_lds_cur_t c; eset_lds(&KERN<true>, lds, c); hipLaunchKernelGGL((KERN<true>), grid, dim3(NTHR), lds, s, args); }    \
-    else { static lako_lds_cur_t c; eset_lds(&KERN<false>, lds, c); hipLaunchKernelGGL((KERN<false>), grid, dim3(NTHR), lds, s, args); }       \
-  } while (0)
-
 }  // namespace
 
 #ifdef LAKO_EXPERIMENTS
@@ -1862,10 +1840,9 @@ extern "C" int lako_exp_attn_stamps(void* host_dst, size_t bytes) {
 }
 #endif
 
-// Shapes the fast path takes (attn.hip asks before falling back to its generic kernels).
-bool lako_attn_enc_supported(const AttnArgs& a, int dtype, int d_head) {
-  static const bool off = getenv("LAKO_ATTN_FAST") && atoi(getenv("LAKO_ATTN_FAST")) == 0;   // A/B against the generic kernels
-  if (off) return false;
+// Shapes the fast path takes (a term of attn_fwd_plan / attn_bwd_plan, attn.hip: everything else runs the generic kernels).
+bool attn_enc_supported(const AttnArgs& a, int dtype, int d_head, const AttnKnobs& kn) {
+  if (!kn.fast) return false;
   if (dtype != LAKO_BF16 || d_head != 64 || a.causal || a.scores_out || a.key_mask) return false;
   if (a.Lk > 256 || a.Lq > 256 || a.Lk < 1) return false;
   if (a.rel_bias && !(a.R == a.Lq + a.Lk - 1 && a.rel_off == a.Lq - 1)) return false;   // the encoder's table: no index clamping
@@ -1878,12 +1855,13 @@ bool lako_attn_enc_supported(const AttnArgs& a, int dtype, int d_head) {
 // with rel_off = 0 that is NEGATIVE for queries past 16 + 4g, i.e. the bytes in front of the copies — the tail rows of an image
 // (zeros by luck while the sequence ends ≥ 4 rows before the image does; an image pair nothing was staged into in the persistent
 // kernels: found by tests/test_kernels_gpu.py::test_attention[enc_fast_nobias-bf16_persistent]).  Index like the encoder's table.
-static void enorm_nobias(AttnArgs& a) {
+static AttnArgs enorm_nobias(AttnArgs a) {
   if (!a.rel_bias) {
     a.R = a.Lq + a.Lk - 1;
     a.rel_off = a.Lq - 1;
     a.drel = nullptr;          // no table, no table gradient
   }
+  return a;
 }
 
 // Which passes run their persistent kernel: LAKO_ATTN_PERSIST is a bit mask — 1 forward, 2 dQ pass, 4 dK/dV pass, 8 = also for
@@ -1892,131 +1870,130 @@ static void enorm_nobias(AttnArgs& a) {
 // forward 146 against 126 — with one 16-wave workgroup per CU every item is a barrier-to-barrier phase whose length is ONE wave's
 // dependency chain; the per-item kernels' two independent workgroups per CU hide that better than the next item's DMA does, except
 // in the dQ pass, whose per-item kernel re-stages K / V three times per workgroup and keeps 4 query blocks per wave.
-static bool epersist(int bit, const AttnArgs& a) {
-  const char* pe = getenv("LAKO_ATTN_PERSIST");      // read per call: a test switches it
-  const int m = pe ? atoi(pe) : 18;
+static bool epersist(int bit, const AttnArgs& a, const AttnKnobs& kn) {
+  const int m = kn.persist;
   return (m & bit) && a.H <= 256 && ((int64_t)a.Bn * a.H >= 1024 || (m & 8));
 }
 
-int lako_attn_enc_fwd(AttnArgs& a, hipStream_t s) {
-#ifdef LAKO_EXPERIMENTS
-  static const int dbg = getenv("LAKO_ATTN_DEBUG") ? atoi(getenv("LAKO_ATTN_DEBUG")) : 0;
-  a.dbg_flags = dbg;
-  a.dbg_buf = (dbg & 262144) ? lako_exp_fwd_stamp_buffer() : nullptr;
-#endif
-  enorm_nobias(a);
-  a.chunk_rows = ((a.Lk + 31) / 32) * 32;
-  const int nqb = (a.Lq + 15) / 16;
-  // persistent form: one 16-wave workgroup per CU walking the sequences of one head (see epersist)
-  if (epersist(1, a) && (int64_t)a.kst * 2 * 256 < (1ll << 31) && (int64_t)a.vst * 2 * 256 < (1ll << 31)) {
-    const int nslots = std::min(a.Bn, std::max(1, 256 / a.H));
-    const int lds = efwdp_lds(a.chunk_rows);
-    EDISPATCH(enc_fwd_p_kernel, PF_NW * 64, a.drop_t16 != 0, dim3(a.H * nslots), lds, s, a);
-    return 0;
-  }
-  a.blocks_per_wg = eblocks_per_wg(nqb, (int64_t)a.Bn * a.H, FWD_NW);
-  const int lds = efwd_lds(a.chunk_rows);
-  const dim3 grid((nqb + a.blocks_per_wg - 1) / a.blocks_per_wg, a.H, a.Bn);
-  // K / V by LDS-DMA, everything in flight together (LAKO_ATTN_FWD_DMA=0: register staging, three round trips)
-  static const bool dma_off = getenv("LAKO_ATTN_FWD_DMA") && atoi(getenv("LAKO_ATTN_FWD_DMA")) == 0;
-  if (!dma_off && (int64_t)a.kst * 2 * 256 < (1ll << 31) && (int64_t)a.vst * 2 * 256 < (1ll << 31)) {
-    EDISPATCH(enc_fwd_c_kernel, FWD_NW * 64, a.drop_t16 != 0, grid, lds, s, a);
-    return 0;
-  }
-  EDISPATCH(enc_fwd_kernel, FWD_NW * 64, a.drop_t16 != 0, grid, lds, s, a);
-  return 0;
+// a persistent launch: one 16-wave workgroup per CU walking the sequences of one head
+static AttnLaunch& eplan_persistent(AttnPlan& pl, const AttnArgs& a, int kernel, int rows, int lds) {
+  AttnLaunch& l = attn_plan_add(pl, a, kernel, PF_NW * 64);
+  l.drop = a.drop_t16 != 0;
+  l.chunk_rows = rows;
+  l.gx = a.H * attn_nslots(a);
+  l.lds = lds;
+  return l;
 }
 
-int lako_attn_enc_bwd(AttnArgs& a, hipStream_t s) {
-#ifdef LAKO_EXPERIMENTS
-  static const int dbg = getenv("LAKO_ATTN_DEBUG") ? atoi(getenv("LAKO_ATTN_DEBUG")) : 0;
-  a.dbg_flags = dbg;
-  if (dbg & 256) goto dkv_pass;      // time the passes separately
-#endif
-  enorm_nobias(a);
-  // one-pass backward (round 5, the default where its LDS layout fits): bit 16 of LAKO_ATTN_PERSIST (default 18 = persistent dQ pass as the
-  // fallback + the fused kernel); a ring of 4 stages where 160 KiB hold it (<= 256 key rows do), else 3
-  {
-    const char* pe = getenv("LAKO_ATTN_PERSIST");      // read per call: a test switches it
-    const int m = pe ? atoi(pe) : 18;
-    const int rows = ((a.Lk + 31) / 32) * 32;
-    const bool fits32 = (int64_t)a.kst * 2 * 256 < (1ll << 31) && (int64_t)a.vst * 2 * 256 < (1ll << 31) && (int64_t)a.qst * 2 * 256 < (1ll << 31) &&
-                        (int64_t)a.ost * 2 * 256 < (1ll << 31);
-    // one addressing form for ragged and padded launches (row offset × token stride): the batch strides must be whole rows, the same number
-    // on every tensor of a side; dq / dk / dv share the strides of q / k / v by contract
-    const bool ragged = a.q_off && a.k_off;
-    const bool padded = !a.q_off && !a.k_off && a.qst > 0 && a.ost > 0 && a.kst > 0 && a.vst > 0 && a.qsb % a.qst == 0 && a.osb % a.ost == 0 &&
-                        a.qsb / a.qst == a.osb / a.ost && a.ksb % a.kst == 0 && a.vsb % a.vst == 0 && a.ksb / a.kst == a.vsb / a.vst &&
-                        a.qsb / a.qst * a.Bn < (1ll << 31) && a.ksb / a.kst * a.Bn < (1ll << 31);
-    if ((m & 16 || a.det) && a.H <= 256 && fits32 && (ragged || padded) && rows <= 224 && a.Lq <= 256 && efb_lds(rows, 3) <= 160 * 1024 &&
-        (!a.det || a.H * a.R <= lako_det::SLOTS)) {
-      AttnArgs f = a;
-      f.chunk_rows = rows;
-      f.rq = padded ? (int)(a.qsb / a.qst) : 0;
-      f.rk = padded ? (int)(a.ksb / a.kst) : 0;
-      const int nslots = std::min(a.Bn, std::max(1, 256 / a.H));
-      const bool drop = a.drop_t16 != 0;
-      // (read on every call, as LAKO_ATTN_PERSIST above: tests switch the ring depth inside one process — cached in a static the first
-      //  fused launch would fix it for the whole run and the three-stage instantiations would never be exercised)
-      const char* nst_s = getenv("LAKO_ATTN_FUSED_NST");
-      const int nst_env = nst_s ? atoi(nst_s) : 4;
-      const int nst = (nst_env >= 4 && efb_lds(rows, 4) <= 160 * 1024) ? 4 : 3;
-      const int lds = efb_lds(rows, nst);
-      const dim3 grid(a.H * nslots);
-#ifdef LAKO_EXPERIMENTS
-      if (f.dbg_flags & 131072) f.scores_out = reinterpret_cast<float*>(lako_exp_stamp_buffer());
-#endif
-#define EFB(D, N)                                                                                          \
-  do {                                                                                                     \
-    static lako_lds_cur_t c;                                                                               \
-    eset_lds(&enc_bwd_fused_kernel<D, N>, lds, c);                                                         \
-    hipLaunchKernelGGL((enc_bwd_fused_kernel<D, N>), grid, dim3(FB_NW * 64), lds, s, f);                   \
-  } while (0)
-      if (nst == 4) { if (drop) EFB(true, 4); else EFB(false, 4); }
-      else { if (drop) EFB(true, 3); else EFB(false, 3); }
-#undef EFB
-      return 0;
-    }
+void attn_enc_fwd_plan(const AttnArgs& a0, const AttnKnobs& kn, AttnPlan& pl) {
+  const AttnArgs a = enorm_nobias(a0);
+  const int rows = roundup32(a.Lk);
+  // persistent form (see epersist)
+  if (epersist(1, a, kn) && fits32(a.kst) && fits32(a.vst)) {
+    eplan_persistent(pl, a, LAKO_ATTN_ENC_FWD_P, rows, efwdp_lds(rows));
+    return;
   }
-  // LAKO_DETERMINISTIC: the two-pass kernels below add into the workgroup's bias-gradient table by LDS float atomics in arrival order —
-  // not taken in that mode: the caller runs the generic kernels (attn.hip), whose contributions go through det.h
-  if (a.det) return 1;
+  // K / V by LDS-DMA, everything in flight together (LAKO_ATTN_FWD_DMA=0: register staging, three round trips)
+  const bool dma = kn.fwd_dma && fits32(a.kst) && fits32(a.vst);
+  AttnLaunch& l = attn_plan_add(pl, a, dma ? LAKO_ATTN_ENC_FWD_C : LAKO_ATTN_ENC_FWD, FWD_NW * 64);
+  const int nqb = (a.Lq + 15) / 16;
+  l.drop = a.drop_t16 != 0;
+  l.chunk_rows = rows;
+  l.blocks_per_wg = blocks_per_wg(nqb, (int64_t)a.Bn * a.H, FWD_NW);
+  l.gx = (nqb + l.blocks_per_wg - 1) / l.blocks_per_wg, l.gy = a.H, l.gz = a.Bn;
+  l.lds = efwd_lds(rows);
+}
+
+// one addressing form for ragged and padded launches of the one-pass backward (row offset × token stride): the batch strides must be whole
+// rows, the same number on every tensor of a side; dq / dk / dv share the strides of q / k / v by contract
+static bool efb_padded(const AttnArgs& a) {
+  return !a.q_off && !a.k_off && a.qst > 0 && a.ost > 0 && a.kst > 0 && a.vst > 0 && a.qsb % a.qst == 0 && a.osb % a.ost == 0 &&
+         a.qsb / a.qst == a.osb / a.ost && a.ksb % a.kst == 0 && a.vsb % a.vst == 0 && a.ksb / a.kst == a.vsb / a.vst &&
+         a.qsb / a.qst * a.Bn < (1ll << 31) && a.ksb / a.kst * a.Bn < (1ll << 31);
+}
+
+// one-pass backward (round 5, the default where its LDS layout fits): bit 16 of LAKO_ATTN_PERSIST (default 18 = persistent dQ pass as the
+// fallback + the fused kernel), and always in LAKO_DETERMINISTIC mode (its bias gradient goes through det.h)
+bool attn_enc_fused_fits(const AttnArgs& a0, const AttnKnobs& kn) {
+  if (ATTN_DBG(kn, 256)) return false;      // (experiments) time the passes separately: the dK/dV pass alone
+  const AttnArgs a = enorm_nobias(a0);
+  const int rows = roundup32(a.Lk);
+  const bool ragged = a.q_off && a.k_off;
+  return (kn.persist & 16 || kn.det) && a.H <= 256 && fits32(a.kst) && fits32(a.vst) && fits32(a.qst) && fits32(a.ost) &&
+         (ragged || efb_padded(a)) && rows <= 224 && a.Lq <= 256 && efb_lds(rows, 3) <= 160 * 1024 &&
+         (!kn.det || a.H * a.R <= lako_det::SLOTS);
+}
+
+void attn_enc_fused_plan(const AttnArgs& a0, const AttnKnobs& kn, AttnPlan& pl) {
+  const AttnArgs a = enorm_nobias(a0);
+  const int rows = roundup32(a.Lk);
+  const bool padded = efb_padded(a);
+  AttnLaunch& l = attn_plan_add(pl, a, LAKO_ATTN_ENC_BWD_FUSED, FB_NW * 64);
+  l.drop = a.drop_t16 != 0;
+  l.chunk_rows = rows;
+  l.rq = padded ? (int)(a.qsb / a.qst) : 0;
+  l.rk = padded ? (int)(a.ksb / a.kst) : 0;
+  // a ring of 4 stages where 160 KiB hold it (<= 256 key rows do), else 3
+  l.ring = (kn.fused_nst >= 4 && efb_lds(rows, 4) <= 160 * 1024) ? 4 : 3;
+  l.lds = efb_lds(rows, l.ring);
+  l.gx = a.H * attn_nslots(a);
+}
+
+// dQ pass, then dK/dV pass.  (They add into the workgroup's bias-gradient table by LDS float atomics in arrival order: attn_bwd_plan does
+// not take them in LAKO_DETERMINISTIC mode.)
+void attn_enc_two_pass_plan(const AttnArgs& a0, const AttnKnobs& kn, AttnPlan& pl) {
+  const AttnArgs a = enorm_nobias(a0);
   {  // dQ pass: every query block of a sequence in one workgroup, several batch rows per workgroup (bias gradient in registers)
-    AttnArgs q = a;
-    q.chunk_rows = ((a.Lk + 31) / 32) * 32;
-    if (epersist(2, a) && (int64_t)a.kst * 2 * 256 < (1ll << 31) && (int64_t)a.vst * 2 * 256 < (1ll << 31)) {
-      const int nslots = std::min(a.Bn, std::max(1, 256 / a.H));
-      EDISPATCH(enc_bwd_dq_p_kernel, PF_NW * 64, a.drop_t16 != 0, dim3(a.H * nslots), ebwd0p_lds(q.chunk_rows), s, q);
+    const int rows = roundup32(a.Lk);
+    if (epersist(2, a, kn) && fits32(a.kst) && fits32(a.vst)) {
+      eplan_persistent(pl, a, LAKO_ATTN_ENC_BWD_DQ_P, rows, ebwd0p_lds(rows));
     } else {
-      const int64_t wgs = (int64_t)a.Bn * a.H;
-      static const int wg_target = getenv("LAKO_ATTN_WGS") ? atoi(getenv("LAKO_ATTN_WGS")) : 1024;
-      q.bn_per_wg = (int)(wgs / wg_target > 1 ? wgs / wg_target : 1);
-      if (q.bn_per_wg > OFFS_MAX - 1) q.bn_per_wg = OFFS_MAX - 1;
-      const int lds = ebwd0_lds(q.chunk_rows);
-      const dim3 grid(1, a.H, (a.Bn + q.bn_per_wg - 1) / q.bn_per_wg);
-      EDISPATCH(enc_bwd_dq_kernel, 256, a.drop_t16 != 0, grid, lds, s, q);
+      AttnLaunch& l = attn_plan_add(pl, a, LAKO_ATTN_ENC_BWD_DQ, 256);
+      l.drop = a.drop_t16 != 0;
+      l.chunk_rows = rows;
+      l.bn_per_wg = attn_bn_per_wg((int64_t)a.Bn * a.H, kn);
+      l.gy = a.H, l.gz = (a.Bn + l.bn_per_wg - 1) / l.bn_per_wg;
+      l.lds = ebwd0_lds(rows);
     }
   }
-#ifdef LAKO_EXPERIMENTS
-  if (a.dbg_flags & 512) return 0;
-dkv_pass:
-#endif
   {  // dK/dV pass
-    AttnArgs k = a;
-    k.chunk_rows = ((a.Lq + 31) / 32) * 32;
-    const int nkb = (a.Lk + 15) / 16;
-    if (epersist(4, a) && (int64_t)a.qst * 2 * 256 < (1ll << 31) && (int64_t)a.ost * 2 * 256 < (1ll << 31)) {
-      const int nslots = std::min(a.Bn, std::max(1, 256 / a.H));
-      const int lds = ebwd1p_lds(k.chunk_rows);
-      EDISPATCH(enc_bwd_dkv_p_kernel, PF_NW * 64, a.drop_t16 != 0, dim3(a.H * nslots), lds, s, k);
-      return 0;
+    const int rows = roundup32(a.Lq);
+    if (epersist(4, a, kn) && fits32(a.qst) && fits32(a.ost)) {
+      eplan_persistent(pl, a, LAKO_ATTN_ENC_BWD_DKV_P, rows, ebwd1p_lds(rows));
+    } else {
+      AttnLaunch& l = attn_plan_add(pl, a, LAKO_ATTN_ENC_BWD_DKV, DKV_NW * 64);
+      const int nkb = (a.Lk + 15) / 16;
+      l.drop = a.drop_t16 != 0;
+      l.chunk_rows = rows;
+      l.dma_stage = kn.dkv_dma && fits32(a.qst) && fits32(a.ost);
+      l.blocks_per_wg = blocks_per_wg(nkb, (int64_t)a.Bn * a.H, DKV_NW);
+      l.gx = (nkb + l.blocks_per_wg - 1) / l.blocks_per_wg, l.gy = a.H, l.gz = a.Bn;
+      l.lds = ebwd1_lds(rows);
     }
-    static const bool dkv_dma_off = getenv("LAKO_ATTN_DKV_DMA") && atoi(getenv("LAKO_ATTN_DKV_DMA")) == 0;
-    k.dma_stage = !dkv_dma_off && (int64_t)a.qst * 2 * 256 < (1ll << 31) && (int64_t)a.ost * 2 * 256 < (1ll << 31);
-    k.blocks_per_wg = eblocks_per_wg(nkb, (int64_t)a.Bn * a.H, DKV_NW);
-    const int lds = ebwd1_lds(k.chunk_rows);
-    const dim3 grid((nkb + k.blocks_per_wg - 1) / k.blocks_per_wg, a.H, a.Bn);
-    EDISPATCH(enc_bwd_dkv_kernel, DKV_NW * 64, a.drop_t16 != 0, grid, lds, s, k);
   }
-  return 0;
+  // (experiments) time the passes separately: 256 drops the dQ pass from the plan, 512 the dK/dV pass
+  if (ATTN_DBG(kn, 256)) pl.launch[0] = pl.launch[1];
+  if (ATTN_DBG(kn, 256 | 512)) pl.n_launches = 1;
+}
+
+void attn_enc_launch(const AttnLaunch& l, AttnArgs x, const AttnKnobs& kn, hipStream_t s) {
+#ifdef LAKO_EXPERIMENTS   // the debug bits and the stamp buffers attach here, where the plan is executed
+  x.dbg_flags = kn.dbg_flags;
+  if (l.kernel <= LAKO_ATTN_ENC_FWD_P) x.dbg_buf = (x.dbg_flags & 262144) ? lako_exp_fwd_stamp_buffer() : nullptr;
+  if (l.kernel == LAKO_ATTN_ENC_BWD_FUSED && (x.dbg_flags & 131072)) x.scores_out = reinterpret_cast<float*>(lako_exp_stamp_buffer());
+#endif
+#define EDROP(KERN) (l.drop ? attn_launch<&KERN<true>>(l, x, s) : attn_launch<&KERN<false>>(l, x, s))
+  switch (l.kernel) {
+    case LAKO_ATTN_ENC_FWD: return EDROP(enc_fwd_kernel);
+    case LAKO_ATTN_ENC_FWD_C: return EDROP(enc_fwd_c_kernel);
+    case LAKO_ATTN_ENC_FWD_P: return EDROP(enc_fwd_p_kernel);
+    case LAKO_ATTN_ENC_BWD_DQ: return EDROP(enc_bwd_dq_kernel);
+    case LAKO_ATTN_ENC_BWD_DQ_P: return EDROP(enc_bwd_dq_p_kernel);
+    case LAKO_ATTN_ENC_BWD_DKV: return EDROP(enc_bwd_dkv_kernel);
+    case LAKO_ATTN_ENC_BWD_DKV_P: return EDROP(enc_bwd_dkv_p_kernel);
+    default:
+      if (l.ring == 4) return l.drop ? attn_launch<&enc_bwd_fused_kernel<true, 4>>(l, x, s) : attn_launch<&enc_bwd_fused_kernel<false, 4>>(l, x, s);
+      return l.drop ? attn_launch<&enc_bwd_fused_kernel<true, 3>>(l, x, s) : attn_launch<&enc_bwd_fused_kernel<false, 3>>(l, x, s);
+  }
+#undef EDROP
 }

@@ -4,9 +4,11 @@
 #include <float.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
+#include "det.h"
 
 #ifdef LAKO_EXPERIMENTS
 #define ATTN_DBG(a, bits) ((a).dbg_flags & (bits))
@@ -18,6 +20,8 @@ constexpr int CH_MAX = 256;  // LDS-side rows per chunk
 constexpr int OFFS_MAX = 64; // batch rows per workgroup (+1) whose ragged offsets are staged in LDS
 
 template <typename T, int DK> struct AC {
+  using Elem = T;
+  static constexpr int DHEAD = DK;
   static constexpr int ES = sizeof(T);
   static constexpr int ROWB = DK * ES + 16;   // padded LDS row
   static constexpr int CPR = DK * ES / 16;    // 16-B chunks per row
@@ -141,7 +145,113 @@ __device__ __forceinline__ void drop_keep_col(uint32_t h, const DropCol& c, uint
   for (int r = 0; r < 4; ++r) k[r] = (drop_mix(h, c.m[r], c.s[r]) << c.sh) >= t_hi;
 }
 
-// fast path of attn_enc.hip (bf16, d_head 64, <= 256 keys, no causal mask, no score capture); attn.hip dispatches
-bool lako_attn_enc_supported(const AttnArgs& a, int dtype, int d_head);
-int lako_attn_enc_fwd(AttnArgs& a, hipStream_t s);
-int lako_attn_enc_bwd(AttnArgs& a, hipStream_t s);
+// ---- host side: decide, then launch ---------------------------------------------------------------------------------------------
+// attn_fwd_plan / attn_bwd_plan (attn.hip) turn (arguments, dtype, d_head, knobs) into a plan: which kernel(s), in which form, over which
+// grid, with how much LDS and with which derived AttnArgs fields.  They are pure: no HIP call, no pointer dereferenced, nothing launched.
+// attn_run (attn.hip) executes a plan; lako_attn_fwd_plan / lako_attn_bwd_plan hand the very same plan to the caller (lako_hip.h
+// describes its fields).  The fast path's share of the decision and of the launching sits next to its kernels in attn_enc.hip.
+using AttnLaunch = lako_attn_launch_t;
+using AttnPlan = lako_attn_plan_t;
+
+// the environment knobs of both files, filled in one place (attn_knobs below)
+struct AttnKnobs {
+  // read on EVERY call: tests switch them inside one process (cached in a static, the first launch would fix them for the whole run and
+  // the other kernels / the three-stage instantiations would never be exercised)
+  int persist;     // LAKO_ATTN_PERSIST: bit mask, see attn_persist
+  int fused_nst;   // LAKO_ATTN_FUSED_NST: ring stages of the one-pass backward (default 4)
+  // read once per process
+  bool fast;       // LAKO_ATTN_FAST=0 clears it: A/B against the generic kernels
+  bool fwd_dma;    // LAKO_ATTN_FWD_DMA=0 clears it: the per-item forward stages K / V through registers, three round trips
+  bool dkv_dma;    // LAKO_ATTN_DKV_DMA=0 clears it: the same for the per-item dK/dV pass
+  int wg_target;   // LAKO_ATTN_WGS: workgroups the per-item dQ passes aim for (default 1024)
+  bool det;        // LAKO_DETERMINISTIC=1 (det.h)
+  int dbg_flags;   // LAKO_ATTN_DEBUG, timing experiments (-DLAKO_EXPERIMENTS; always 0 in the release library)
+};
+constexpr int ATTN_PERSIST_DEFAULT = 18;   // persistent dQ pass as the fallback + the one-pass backward
+inline AttnKnobs attn_knobs() {
+  static const AttnKnobs once = [] {
+    const auto off = [](const char* name) { return getenv(name) && atoi(getenv(name)) == 0; };
+    AttnKnobs k = {};
+    k.fast = !off("LAKO_ATTN_FAST");
+    k.fwd_dma = !off("LAKO_ATTN_FWD_DMA");
+    k.dkv_dma = !off("LAKO_ATTN_DKV_DMA");
+    k.wg_target = getenv("LAKO_ATTN_WGS") ? atoi(getenv("LAKO_ATTN_WGS")) : 1024;
+    k.det = lako_det::on();
+#ifdef LAKO_EXPERIMENTS   // timing experiments (bits 4 / 8 drop the bias-gradient flushes: wrong results) — never in the release library
+    k.dbg_flags = getenv("LAKO_ATTN_DEBUG") ? atoi(getenv("LAKO_ATTN_DEBUG")) : 0;
+#endif
+    return k;
+  }();
+  AttnKnobs kn = once;
+  const char* pe = getenv("LAKO_ATTN_PERSIST");
+  const char* nst = getenv("LAKO_ATTN_FUSED_NST");
+  kn.persist = pe ? atoi(pe) : ATTN_PERSIST_DEFAULT;
+  kn.fused_nst = nst ? atoi(nst) : 4;
+  return kn;
+}
+
+// a buffer descriptor of 256 rows of this token stride (bf16 elements) stays inside the 32-bit range
+inline bool fits32(int64_t stride) { return stride * 2 * 256 < (1ll << 31); }
+inline int roundup32(int L) { return ((L + 31) / 32) * 32; }
+// workgroups per head of a persistent kernel (256 CUs)
+inline int attn_nslots(const AttnArgs& a) { return std::min(a.Bn, std::max(1, 256 / a.H)); }
+// query / key blocks per workgroup of nw waves: all of them when there are already plenty of workgroups, otherwise split so that the grid
+// reaches ~1024 workgroups (multiples of the workgroup's wave count; no LDS-side merge needed: blocks are independent)
+inline int blocks_per_wg(int nblocks, int64_t bh, int nw) {
+  const int64_t want = 1024;
+  if (bh >= want || nblocks <= nw) return ((nblocks + nw - 1) / nw) * nw;
+  const int groups = (int)((want + bh - 1) / bh);
+  int per = (nblocks + groups - 1) / groups;
+  per = ((per + nw - 1) / nw) * nw;
+  return per < nw ? nw : per;
+}
+// batch rows one workgroup of a per-item dQ pass walks (bias gradient accumulated in registers); the kernels stage bn_per_wg + 1 row
+// offsets in LDS
+inline int attn_bn_per_wg(int64_t wgs, const AttnKnobs& kn) {
+  const int bn = (int)(wgs / kn.wg_target > 1 ? wgs / kn.wg_target : 1);
+  return bn > OFFS_MAX - 1 ? OFFS_MAX - 1 : bn;
+}
+
+// next launch of a plan, carrying the caller's bias table as it is
+inline AttnLaunch& attn_plan_add(AttnPlan& pl, const AttnArgs& a, int kernel, int block) {
+  AttnLaunch& l = pl.launch[pl.n_launches++];
+  l.kernel = kernel;
+  l.block = block;
+  l.gx = l.gy = l.gz = 1;
+  l.R = a.R;
+  l.rel_off = a.rel_off;
+  l.drel = a.drel != nullptr;
+  return l;
+}
+// what that launch's kernel receives: the caller's arguments + the plan's derived fields
+inline AttnArgs attn_launch_args(const AttnArgs& a, const AttnLaunch& l) {
+  AttnArgs x = a;
+  x.chunk_rows = l.chunk_rows;
+  x.blocks_per_wg = l.blocks_per_wg;
+  x.bn_per_wg = l.bn_per_wg;
+  x.dma_stage = l.dma_stage;
+  x.rq = l.rq;
+  x.rk = l.rk;
+  x.grid_x = l.grid_x;
+  x.grid_z = l.grid_z;
+  x.R = l.R;
+  x.rel_off = l.rel_off;
+  if (!l.drel) x.drel = nullptr;
+  return x;
+}
+// Launch one instantiation.  It owns that instantiation's lako_lds_cur_t: the kernel's dynamic-LDS limit is raised only when a launch needs
+// more than any earlier one ON THIS DEVICE (the attribute is per device: common.h).
+template <auto KERN>
+void attn_launch(const AttnLaunch& l, const AttnArgs& x, hipStream_t s) {
+  static lako_lds_cur_t cur;
+  lako_raise_max_lds(reinterpret_cast<const void*>(KERN), l.lds, cur);
+  hipLaunchKernelGGL(KERN, dim3(l.gx, l.gy, l.gz), dim3(l.block), l.lds, s, x);
+}
+
+// fast path of attn_enc.hip (bf16, d_head 64, <= 256 keys, no causal mask, no score capture): its terms of the plan and its launches
+bool attn_enc_supported(const AttnArgs& a, int dtype, int d_head, const AttnKnobs& kn);
+bool attn_enc_fused_fits(const AttnArgs& a, const AttnKnobs& kn);
+void attn_enc_fwd_plan(const AttnArgs& a, const AttnKnobs& kn, AttnPlan& pl);
+void attn_enc_fused_plan(const AttnArgs& a, const AttnKnobs& kn, AttnPlan& pl);
+void attn_enc_two_pass_plan(const AttnArgs& a, const AttnKnobs& kn, AttnPlan& pl);
+void attn_enc_launch(const AttnLaunch& l, AttnArgs x, const AttnKnobs& kn, hipStream_t s);

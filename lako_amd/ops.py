@@ -15,7 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import (EPI_ATOMIC, EPI_AUXMASK, EPI_GATED, EPI_GATED_BWD, EPI_NORM_A, EPI_RELU, EPI_RESID, LAKO_BF16, LAKO_F32, LAKO_FP8_E4M3, AttnBwd, AttnFwd, Dropout,
+from ._lib import (EPI_ATOMIC, EPI_AUXMASK, EPI_GATED, EPI_GATED_BWD, EPI_NORM_A, EPI_RELU, EPI_RESID, LAKO_BF16, LAKO_F32, LAKO_FP8_E4M3, AttnBwd, AttnFwd, AttnPlan, Dropout,
                    GemmNT, GemmPlan, GemmTNPlan, LakoError, NO_DROP, check)
 
 
@@ -462,8 +462,9 @@ class HipOps:
             raise LakoError(f"attention: order must be a contiguous int32 permutation of the {Bn} sequences")
         return order.data_ptr()
 
-    def attn_fwd(self, q, k, v, out, stats, *, rel_bias=None, rel_off=0, key_mask=None, causal=False, causal_off=0,
-                 drop=None, scores_out=None, q_off=None, k_off=None, max_q=None, max_k=None, order=None):
+    def _attn_fwd_struct(self, q, k, v, out, stats, rel_bias, rel_off, key_mask, causal, causal_off, drop, scores_out, q_off, k_off, max_q,
+                         max_k, order):
+        """the lako_attn_fwd_t of a call: what attn_fwd launches and attn_fwd_plan asks about"""
         p = AttnFwd()
         Bn, Lq, Lk, H, dk = self._ragged(p, q, k, q_off, k_off, max_q, max_k)
         p.order = self._order(order, Bn)
@@ -485,10 +486,26 @@ class HipOps:
         p.drop = _drop(drop)
         if scores_out is not None:
             p.scores_out = scores_out.data_ptr()
-        self._timed("attn_fwd", 4.0 * Bn * H * Lq * Lk * dk, lambda: check(self.lib.lako_attn_fwd(C.byref(p), self._stream()), "lako_attn_fwd"))
+        return p
 
-    def attn_bwd(self, q, k, v, out, dout, stats, dq, dk_, dv, *, rel_bias=None, drel=None, rel_off=0, key_mask=None,
-                 causal=False, causal_off=0, drop=None, q_off=None, k_off=None, max_q=None, max_k=None, order=None):
+    def attn_fwd(self, q, k, v, out, stats, *, rel_bias=None, rel_off=0, key_mask=None, causal=False, causal_off=0,
+                 drop=None, scores_out=None, q_off=None, k_off=None, max_q=None, max_k=None, order=None):
+        p = self._attn_fwd_struct(q, k, v, out, stats, rel_bias, rel_off, key_mask, causal, causal_off, drop, scores_out, q_off, k_off, max_q,
+                                  max_k, order)
+        self._timed("attn_fwd", 4.0 * p.Bn * p.H * p.Lq * p.Lk * p.d_head, lambda: check(self.lib.lako_attn_fwd(C.byref(p), self._stream()), "lako_attn_fwd"))
+
+    def attn_fwd_plan(self, q, k, v, out, stats, *, rel_bias=None, rel_off=0, key_mask=None, causal=False, causal_off=0,
+                      drop=None, scores_out=None, q_off=None, k_off=None, max_q=None, max_k=None, order=None):
+        """the launch attn_fwd would make for these arguments (lako_attn_fwd_plan: the same struct, nothing launched)"""
+        p = self._attn_fwd_struct(q, k, v, out, stats, rel_bias, rel_off, key_mask, causal, causal_off, drop, scores_out, q_off, k_off, max_q,
+                                  max_k, order)
+        plan = AttnPlan()
+        check(self.lib.lako_attn_fwd_plan(C.byref(p), C.byref(plan)), "lako_attn_fwd_plan")
+        return plan
+
+    def _attn_bwd_struct(self, q, k, v, out, dout, stats, dq, dk_, dv, rel_bias, drel, rel_off, key_mask, causal, causal_off, drop, q_off,
+                         k_off, max_q, max_k, order):
+        """the lako_attn_bwd_t of a call: what attn_bwd launches and attn_bwd_plan asks about"""
         p = AttnBwd()
         Bn, Lq, Lk, H, dk = self._ragged(p, q, k, q_off, k_off, max_q, max_k)
         p.order = self._order(order, Bn)
@@ -513,7 +530,22 @@ class HipOps:
         p.Bn, p.H, p.Lq, p.Lk, p.d_head = Bn, H, Lq, Lk, dk
         p.dtype = _dt(q)
         p.drop = _drop(drop)
-        self._timed("attn_bwd", 8.0 * Bn * H * Lq * Lk * dk, lambda: check(self.lib.lako_attn_bwd(C.byref(p), self._stream()), "lako_attn_bwd"))
+        return p
+
+    def attn_bwd(self, q, k, v, out, dout, stats, dq, dk_, dv, *, rel_bias=None, drel=None, rel_off=0, key_mask=None,
+                 causal=False, causal_off=0, drop=None, q_off=None, k_off=None, max_q=None, max_k=None, order=None):
+        p = self._attn_bwd_struct(q, k, v, out, dout, stats, dq, dk_, dv, rel_bias, drel, rel_off, key_mask, causal, causal_off, drop, q_off,
+                                  k_off, max_q, max_k, order)
+        self._timed("attn_bwd", 8.0 * p.Bn * p.H * p.Lq * p.Lk * p.d_head, lambda: check(self.lib.lako_attn_bwd(C.byref(p), self._stream()), "lako_attn_bwd"))
+
+    def attn_bwd_plan(self, q, k, v, out, dout, stats, dq, dk_, dv, *, rel_bias=None, drel=None, rel_off=0, key_mask=None,
+                      causal=False, causal_off=0, drop=None, q_off=None, k_off=None, max_q=None, max_k=None, order=None):
+        """the launches attn_bwd would make for these arguments (lako_attn_bwd_plan: the same struct, nothing launched)"""
+        p = self._attn_bwd_struct(q, k, v, out, dout, stats, dq, dk_, dv, rel_bias, drel, rel_off, key_mask, causal, causal_off, drop, q_off,
+                                  k_off, max_q, max_k, order)
+        plan = AttnPlan()
+        check(self.lib.lako_attn_bwd_plan(C.byref(p), C.byref(plan)), "lako_attn_bwd_plan")
+        return plan
 
     # ---- loss / optimizer -----------------------------------------------------------------------
     # ---- cross-attention in the encoder-state space (csrc/xattn.hip) ------------------------------------

@@ -55,7 +55,8 @@ def test_struct_layouts_match_header_order():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     for cname, py in (("lako_gemm_nt_t", _lib.GemmNT), ("lako_attn_fwd_t", _lib.AttnFwd), ("lako_attn_bwd_t", _lib.AttnBwd),
                       ("lako_dropout_t", _lib.Dropout), ("lako_headbatch_t", _lib.HeadBatch),
-                      ("lako_gemm_tn_item_t", _lib.GemmTNItem), ("lako_gemm_plan_t", _lib.GemmPlan), ("lako_gemm_tn_plan_t", _lib.GemmTNPlan)):
+                      ("lako_gemm_tn_item_t", _lib.GemmTNItem), ("lako_gemm_plan_t", _lib.GemmPlan), ("lako_gemm_tn_plan_t", _lib.GemmTNPlan),
+                      ("lako_attn_launch_t", _lib.AttnLaunch)):
         body = re.search(r"typedef struct \{([^{}]*)\}\s*" + cname, src, re.S).group(1)
         names = []
         for decl in body.split(";"):
@@ -126,6 +127,17 @@ def test_bad_arguments_return_error_codes(lib):
     items = (_lib.GemmTNItem * 1)()
     assert L.lako_gemm_tn_grouped_plan(items, 1, 1024, 1, 0, None, None, 0, ctypes.byref(tnplan)) == -1   # null operands / empty problem
     assert L.lako_gemm_tn_grouped_plan(items, 1, 1024, 1, 0, None, None, 0, None) == -1
+    # ... and the attention's: the refusal of the launching call (a above: d_head 48), null structs and outputs, a valid query
+    ap = _lib.AttnPlan()
+    assert L.lako_attn_fwd_plan(ctypes.byref(a), ctypes.byref(ap)) == -4 and ap.n_launches == 0 and ap.launch[0].kernel == 0
+    assert L.lako_attn_fwd_plan(None, ctypes.byref(ap)) == -1 and L.lako_attn_fwd_plan(ctypes.byref(a), None) == -1
+    assert L.lako_attn_bwd_plan(None, ctypes.byref(ap)) == -1 and L.lako_attn_bwd_plan(ctypes.byref(_lib.AttnBwd()), None) == -1
+    assert L.lako_attn_bwd_plan(ctypes.byref(_lib.AttnBwd()), ctypes.byref(ap)) == -1 == L.lako_attn_bwd(ctypes.byref(_lib.AttnBwd()), None)
+    a.q, a.k, a.v, a.out, a.lse, a.d_head = 4096, 8192, 12288, 16384, 20480, 32
+    a.q_stride_b = a.k_stride_b = a.v_stride_b = a.o_stride_b = 4 * 32
+    a.q_stride_t = a.k_stride_t = a.v_stride_t = a.o_stride_t = 32
+    assert L.lako_attn_fwd_plan(ctypes.byref(a), ctypes.byref(ap)) == 0 and ap.n_launches == 1 and ap.launch[0].kernel == _lib.ATTN_FWD
+    assert ctypes.sizeof(_lib.AttnPlan) == 4 + 2 * 20 * 4
 
 
 def test_comm_and_workspace_entry_points_validate_their_arguments(lib):

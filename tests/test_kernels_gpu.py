@@ -2,10 +2,14 @@
 (tests/ref_ops.py), on the same seeded inputs.  fp32 kernels (exact-f32 MFMA) must agree to ~1e-4;
 bf16 kernels are compared against the reference evaluated on the same bf16-rounded inputs with a
 tolerance of a few bf16 ulps of the output scale (stated per test)."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
+from lako_amd._lib import (ATTN_BWD_DKV, ATTN_BWD_DQ, ATTN_ENC_BWD_DKV, ATTN_ENC_BWD_DKV_P, ATTN_ENC_BWD_DQ, ATTN_ENC_BWD_DQ_P, ATTN_ENC_BWD_FUSED,
+                           ATTN_ENC_FWD_C, ATTN_ENC_FWD_P, ATTN_FWD)
 from lako_amd._lib import (NT_128, NT_EIGHT, NT_EIGHT_256x128, NT_FOUR, NT_MX_EIGHT, NT_MX_FOUR, NT_REFUSED, NT_RING, NT_SKINNY,
                            NT_SKINNY_NORM)
 from tests.ref_ops import RefOps, keep_mask
@@ -763,6 +767,7 @@ ATTN_CASES = [
     ("enc_fast_drop", 3, 3, 200, 200, 64, True, False, False, (0.1, 17, 6), True),
     ("enc_fast_odd", 2, 4, 37, 37, 64, True, False, False, (0.1, 18, 7), True),
     ("enc_fast_256", 1, 2, 256, 256, 64, True, False, False, None, True),
+    ("enc_fast_224", 2, 2, 224, 224, 64, True, False, False, (0.1, 19, 9), True),   # the most key rows the one-pass backward holds
     ("enc_fast_nobias", 2, 2, 130, 130, 64, False, False, False, None, True),
     ("dec_self", 4, 12, 7, 7, 64, True, False, True, None, True),
     ("dec_self_drop", 4, 2, 9, 9, 32, True, False, True, (0.1, 12, 4), False),
@@ -770,6 +775,33 @@ ATTN_CASES = [
     ("cross_drop", 2, 2, 20, 300, 32, False, True, False, (0.1, 13, 5), False),
     ("decode_step", 4, 8, 1, 23, 64, True, False, False, None, False),
 ]
+
+
+def fast_fwd_kernel(persist, Bn, H):
+    """the forward a fast-path call (bf16, d_head 64, <= 256 keys, the encoder's bias table or none, no mask, no capture) runs under
+    LAKO_ATTN_PERSIST = persist: bit 1 = the persistent kernel, from 1024 (sequence, head) items on or with bit 8"""
+    m = int(persist)
+    return ATTN_ENC_FWD_P if m & 1 and H <= 256 and (Bn * H >= 1024 or m & 8) else ATTN_ENC_FWD_C
+
+
+def fast_bwd_kernels(ops, persist, Bn, H, Lk, whole_rows=True):
+    """... and its backward: the one-pass kernel (bit 16; always in LAKO_DETERMINISTIC mode) where its layout holds — at most 224 key rows,
+    at most 256 heads, ragged rows or padded batch strides of whole rows — else the dQ (bit 2) and dK/dV (bit 4) passes, persistent under
+    the forward's conditions; in LAKO_DETERMINISTIC mode the generic kernels instead of those two"""
+    m = int(persist)
+    if (m & 16 or ops.det) and H <= 256 and -(-Lk // 32) * 32 <= 224 and whole_rows:
+        return [ATTN_ENC_BWD_FUSED]
+    if ops.det:
+        return [ATTN_BWD_DQ, ATTN_BWD_DKV]
+    pers = lambda bit: bool(m & bit) and H <= 256 and (Bn * H >= 1024 or bool(m & 8))      # noqa: E731
+    return [ATTN_ENC_BWD_DQ_P if pers(2) else ATTN_ENC_BWD_DQ, ATTN_ENC_BWD_DKV_P if pers(4) else ATTN_ENC_BWD_DKV]
+
+
+def planned(query, want, *a, **kw):
+    """assert that the call (*a, **kw) is planned on the kernels `want` (HipOps.attn_fwd_plan / attn_bwd_plan: the plan the launch consumes)"""
+    pl = query(*a, **kw)
+    assert pl.kernels == want, (pl, want)
+    return pl
 
 
 def make_attn(case, T):
@@ -812,10 +844,12 @@ def test_attention(ops, ref, dt, case, monkeypatch):
         if not case[0].startswith("enc_fast"):
             pytest.skip("the one-pass backward serves the encoder fast path only")
         monkeypatch.setenv("LAKO_ATTN_PERSIST", "16")
-        monkeypatch.setenv("LAKO_ATTN_FUSED_NST", "3" if dt.endswith("ring3") else "4")
+        ring = 3 if dt.endswith("ring3") else 4
+        monkeypatch.setenv("LAKO_ATTN_FUSED_NST", str(ring))
         dt = "bf16"
     else:
         monkeypatch.setenv("LAKO_ATTN_PERSIST", "0")
+    persist = os.environ["LAKO_ATTN_PERSIST"]
     T = DT[dt]
     q, k, v, rel, rel_off, km, causal, drop = make_attn(case, T)
     Bn, Lq, H, dk = q.shape
@@ -825,6 +859,7 @@ def test_attention(ops, ref, dt, case, monkeypatch):
     outr = torch.zeros(Bn, Lq, H, dk, device=dev())
     st, stg = torch.zeros(Bn, H, Lq, 4, device=dev()), torch.zeros(Bn, H, Lq, 4, device=dev())
     sc, scr = torch.zeros(Bn, H, Lq, Lk, device=dev()), torch.zeros(Bn, H, Lq, Lk, device=dev())
+    assert planned(ops.attn_fwd_plan, [ATTN_FWD], q, k, v, out, stg, scores_out=sc, **kw).launch[0].capture == 1   # score capture: generic
     ops.attn_fwd(q, k, v, out, stg, scores_out=sc, **kw)
     ref.attn_fwd(q, k, v, outr, st, scores_out=scr, **kw)
     close(sc, scr, T, f"attn scores {case[0]} {dt}")
@@ -852,6 +887,13 @@ def test_attention(ops, ref, dt, case, monkeypatch):
     drel = torch.zeros_like(rel) if rel is not None else None
     drelr = torch.zeros_like(rel) if rel is not None else None
     bkw = dict(rel_bias=rel, rel_off=rel_off, key_mask=km, causal=causal, causal_off=0, drop=drop)
+    # what this parametrisation runs: the fast path for the bf16 runs of the enc_fast cases (padded batch strides of whole rows) — under
+    # LAKO_ATTN_PERSIST=16 the one-pass kernel up to 224 key rows (enc_fast_256: the per-item two-pass kernels, bits 2 and 4 being clear)
+    fast = T == torch.bfloat16 and case[0].startswith("enc_fast")
+    pl = planned(ops.attn_bwd_plan, fast_bwd_kernels(ops, persist, Bn, H, Lk) if fast else [ATTN_BWD_DQ, ATTN_BWD_DKV],
+                 q, k, v, o_in, dout, st, dq, dk_, dv, drel=drel, **bkw)
+    if pl.kernels == [ATTN_ENC_BWD_FUSED] and persist == "16":
+        assert pl.launch[0].ring == ring and pl.launch[0].drop == (drop is not None)
     ops.attn_bwd(q, k, v, o_in, dout, st, dq, dk_, dv, drel=drel, **bkw)
     ref.attn_bwd(q, k, v, o_in, dout, st, dqr, dkr, dvr, drel=drelr, **bkw)
     close(dq, dqr, T, f"attn_bwd dq {case[0]} {dt}", k=2)
@@ -875,6 +917,8 @@ def test_attention_fast_path_forward(ops, ref, case, persist, monkeypatch):
     out = torch.zeros(Bn, Lq, H, dk, dtype=T, device=dev())
     outr = torch.zeros(Bn, Lq, H, dk, device=dev())
     st, stg = torch.zeros(Bn, H, Lq, 4, device=dev()), torch.zeros(Bn, H, Lq, 4, device=dev())
+    pl = planned(ops.attn_fwd_plan, [fast_fwd_kernel(persist, Bn, H)], q, k, v, out, stg, **kw)
+    assert pl.launch[0].drop == (drop is not None)
     ops.attn_fwd(q, k, v, out, stg, **kw)
     ref.attn_fwd(q, k, v, outr, st, **kw)
     close(stg[..., 0], st[..., 0], T, f"fast rowmax {case[0]}")
@@ -904,7 +948,9 @@ def test_attention_persistent_kernels_equal_per_item_kernels(ops, drop, monkeypa
         monkeypatch.setenv("LAKO_ATTN_PERSIST", persist)
         out = torch.zeros(1, rows, H, dk, dtype=T, device=dev())
         st = torch.zeros(len(lens), H, Lmax, 4, device=dev())
-        ops.attn_fwd(q, k, v, out, st, rel_bias=rel, rel_off=Lmax - 1, drop=drop, q_off=off, k_off=off, max_q=Lmax, max_k=Lmax)
+        fkw = dict(rel_bias=rel, rel_off=Lmax - 1, drop=drop, q_off=off, k_off=off, max_q=Lmax, max_k=Lmax)
+        planned(ops.attn_fwd_plan, [ATTN_ENC_FWD_P if persist == "15" else ATTN_ENC_FWD_C], q, k, v, out, st, **fkw)
+        ops.attn_fwd(q, k, v, out, st, **fkw)
         torch.cuda.synchronize()
         res.append((out, st))
     assert torch.equal(res[0][0], res[1][0])
@@ -920,8 +966,11 @@ def test_attention_persistent_kernels_equal_per_item_kernels(ops, drop, monkeypa
         dqkv = torch.zeros(1, rows, 3 * inner, dtype=T, device=dev())
         dq, dk_, dv = (dqkv[:, :, i * inner:(i + 1) * inner].view(1, rows, H, dk) for i in range(3))
         drel = torch.zeros_like(rel)
-        ops.attn_bwd(q, k, v, res[0][0], dout, st, dq, dk_, dv, rel_bias=rel, drel=drel, rel_off=Lmax - 1, drop=drop, q_off=off,
-                     k_off=off, max_q=Lmax, max_k=Lmax)
+        bkw = dict(rel_bias=rel, drel=drel, rel_off=Lmax - 1, drop=drop, q_off=off, k_off=off, max_q=Lmax, max_k=Lmax)
+        want = {"0": [ATTN_ENC_BWD_DQ, ATTN_ENC_BWD_DKV], "15": [ATTN_ENC_BWD_DQ_P, ATTN_ENC_BWD_DKV_P], "16": [ATTN_ENC_BWD_FUSED]}[persist]
+        assert want == fast_bwd_kernels(ops, persist, len(lens), H, Lmax) or ops.det      # (deterministic mode: the one-pass kernel each time)
+        planned(ops.attn_bwd_plan, fast_bwd_kernels(ops, persist, len(lens), H, Lmax), q, k, v, res[0][0], dout, st, dq, dk_, dv, **bkw)
+        ops.attn_bwd(q, k, v, res[0][0], dout, st, dq, dk_, dv, **bkw)
         torch.cuda.synchronize()
         outs.append((dqkv, st, drel))
     # (measured: 121 of 7 000 dq rows differ by ONE bf16 ulp — the compiler contracts p·dP′ into different fused multiply-adds in the
@@ -997,9 +1046,10 @@ def test_attention_fast_path_race_screen(ops, lengths, monkeypatch):
 def test_attention_processing_order_does_not_change_results(ops, persist, monkeypatch):
     """lako_attn_*_t.order (round 4): the order in which the encoder fast path's workgroups take the sequences — longest first for load
     balance — is a pure scheduling choice: forward outputs, statistics, dq / dk / dv are BIT-identical for the natural order, the
-    descending-length order and a random permutation; the bias gradient (float atomics) agrees to summation noise.  Default kernels
-    (persistent dQ pass), all-persistent, and all per-item kernels (the non-persistent dQ kernel walks consecutive sequences and ignores
-    the order)."""
+    descending-length order and a random permutation; the bias gradient (float atomics) agrees to summation noise.  45 sequences x 12
+    heads are 540 items, fewer than the 1024 the persistent kernels start at: LAKO_ATTN_PERSIST=18 (the default) runs the one-pass
+    backward, 2, 7 and 0 all run the per-item kernels (the per-item dQ kernel walks consecutive sequences and ignores the order); the
+    plans are asserted."""
     monkeypatch.setenv("LAKO_ATTN_PERSIST", persist)
     T = torch.bfloat16
     H, dk, Lmax = 12, 64, 200
@@ -1022,11 +1072,15 @@ def test_attention_processing_order_does_not_change_results(ops, persist, monkey
     for od in orders:
         out = torch.zeros(1, rows, inner, dtype=T, device=dev())
         st = torch.zeros(Bn, H, Lmax, 4, device=dev())
+        planned(ops.attn_fwd_plan, [ATTN_ENC_FWD_C], *args, out.unflatten(2, (H, dk)), st, order=od, **kw)
         ops.attn_fwd(*args, out.unflatten(2, (H, dk)), st, order=od, **kw)
         dqkv = torch.zeros_like(qkv)
         drel = torch.zeros_like(rel)
-        ops.attn_bwd(*args, out.unflatten(2, (H, dk)), heads(dout, 0), st, *(heads(dqkv, c) for c in (0, inner, 2 * inner)),
-                     drel=drel, order=od, **{k: v for k, v in kw.items()})
+        bargs = (*args, out.unflatten(2, (H, dk)), heads(dout, 0), st, *(heads(dqkv, c) for c in (0, inner, 2 * inner)))
+        want = [ATTN_ENC_BWD_FUSED] if persist == "18" or ops.det else [ATTN_ENC_BWD_DQ, ATTN_ENC_BWD_DKV]
+        assert want == fast_bwd_kernels(ops, persist, Bn, H, Lmax)
+        planned(ops.attn_bwd_plan, want, *bargs, drel=drel, order=od, **kw)
+        ops.attn_bwd(*bargs, drel=drel, order=od, **kw)
         res.append((out, st.clone(), dqkv, drel))
     for r in res[1:]:
         assert torch.equal(r[0], res[0][0]) and torch.equal(r[2], res[0][2])
@@ -1084,14 +1138,22 @@ def test_attention_ragged_equals_padded(ops, dt, kind):
     nq = Lq
     out_p = torch.zeros(Bn, nq, inner, dtype=T, device=dev())
     st_p = torch.zeros(Bn, H, nq, 4, device=dev())
+    # the padded calls carry a key mask: generic kernels; the ragged bf16 self-attention: the fast path; the ragged cross-attention (6
+    # queries over 150 keys: one query block over many keys) and every fp32 call: generic
+    persist = os.environ.get("LAKO_ATTN_PERSIST", "18")
+    fast = T == torch.bfloat16 and kind != "cross"
+    planned(ops.attn_fwd_plan, [ATTN_FWD], *args_p, out_p.unflatten(2, (H, dk)), st_p, key_mask=km, drop=drop, **bias)
     ops.attn_fwd(*args_p, out_p.unflatten(2, (H, dk)), st_p, key_mask=km, drop=drop, **bias)
     if kind == "cross":
         out_r, st_r = torch.zeros_like(out_p), torch.zeros_like(st_p)
+        planned(ops.attn_fwd_plan, [ATTN_FWD], *args_r, out_r.unflatten(2, (H, dk)), st_r, drop=drop, **bias, **rag)
         ops.attn_fwd(*args_r, out_r.unflatten(2, (H, dk)), st_r, drop=drop, **bias, **rag)
         assert torch.equal(out_r, out_p) and torch.equal(st_r[..., :2], st_p[..., :2])
     else:
         out_r = torch.zeros(1, rows, inner, dtype=T, device=dev())
         st_r = torch.zeros_like(st_p)
+        planned(ops.attn_fwd_plan, [fast_fwd_kernel(persist, Bn, H) if fast else ATTN_FWD], *args_r, out_r.unflatten(2, (H, dk)), st_r, drop=drop,
+                **bias, **rag)
         ops.attn_fwd(*args_r, out_r.unflatten(2, (H, dk)), st_r, drop=drop, **bias, **rag)
         # bf16: the ragged launch runs the fast path (csrc/attn_enc.hip), the padded one (it carries a key mask) the generic kernels —
         # the same math in a different instruction order: equal to bf16 rounding, not bit for bit
@@ -1110,6 +1172,8 @@ def test_attention_ragged_equals_padded(ops, dt, kind):
         ops.attn_bwd(*args_p, out_p.unflatten(2, (H, dk)), dout_p.unflatten(2, (H, dk)), st_p, heads(dq_p, 0), heads(dkv_p, 0),
                      heads(dkv_p, inner), key_mask=km, drop=drop)
         dq_r, dkv_r = torch.zeros_like(q_p), torch.zeros_like(kv_r)
+        planned(ops.attn_bwd_plan, [ATTN_BWD_DQ, ATTN_BWD_DKV], *args_r, out_r.unflatten(2, (H, dk)), dout_p.unflatten(2, (H, dk)), st_r,
+                heads(dq_r, 0), heads(dkv_r, 0), heads(dkv_r, inner), drop=drop, **rag)
         ops.attn_bwd(*args_r, out_r.unflatten(2, (H, dk)), dout_p.unflatten(2, (H, dk)), st_r, heads(dq_r, 0), heads(dkv_r, 0),
                      heads(dkv_r, inner), drop=drop, **rag)
         assert torch.equal(dq_r, dq_p) and torch.equal(dkv_r, pack(dkv_p))
@@ -1117,6 +1181,9 @@ def test_attention_ragged_equals_padded(ops, dt, kind):
         dqkv_p, dqkv_r = torch.zeros_like(qkv_p), torch.zeros_like(qkv_r)
         ops.attn_bwd(*args_p, out_p.unflatten(2, (H, dk)), dout_p.unflatten(2, (H, dk)), st_p, heads(dqkv_p, 0),
                      heads(dqkv_p, inner), heads(dqkv_p, 2 * inner), key_mask=km, drop=drop, drel=drel_p, **bias)
+        planned(ops.attn_bwd_plan, fast_bwd_kernels(ops, persist, Bn, H, Lmax) if fast else [ATTN_BWD_DQ, ATTN_BWD_DKV], *args_r,
+                out_r.unflatten(2, (H, dk)), pack(dout_p).unflatten(2, (H, dk)), st_r, heads(dqkv_r, 0), heads(dqkv_r, inner),
+                heads(dqkv_r, 2 * inner), drop=drop, drel=drel_r, **bias, **rag)
         ops.attn_bwd(*args_r, out_r.unflatten(2, (H, dk)), pack(dout_p).unflatten(2, (H, dk)), st_r, heads(dqkv_r, 0),
                      heads(dqkv_r, inner), heads(dqkv_r, 2 * inner), drop=drop, drel=drel_r, **bias, **rag)
         assert same(dqkv_r, pack(dqkv_p))
