@@ -485,6 +485,14 @@ int lako_headbatch_tn_multi(const lako_headbatch_t* items, int n, lako_stream_t 
 int lako_ce_fwd_bwd(const float* logits, const int64_t* labels, float* loss_out, void* dlogits,
                     const float* upstream, int64_t M, int64_t V, int dtype, lako_stream_t stream);
 
+/* ---- log-probability of given sequences under the LM head (candidate scoring: FiDT5.score) ----
+ * logits fp32 [R*T, V] (R sequences of T tokens, 16-byte aligned, V % 4 == 0); labels [R*T], -100 = ignore;
+ * score[r] = sum over the valid tokens t of logits[r,t,label] - logsumexp_v logits[r,t,:] (fp32, row maximum subtracted),
+ * n_valid[r] = their number; a sequence without a valid label gets 0 / 0.  A label outside [0, V) is ignored like -100.
+ * Every row is read once; all sums run in a fixed order (no atomics): the same input gives the same bits.  No scratch, no sync. */
+int lako_seq_logprob(const float* logits, const int64_t* labels, float* score, int32_t* n_valid, int64_t R, int T,
+                     int64_t V, lako_stream_t stream);
+
 /* ---- optimizer (train_reader.py:76-79; src/util.py:185-227): global-norm clip + HF AdamW with
  * correct_bias=False + decoupled weight decay, one fused pass over the flat parameter buffer ------ */
 /* out[0] += Σ g²  (caller zeroes out[0]) */

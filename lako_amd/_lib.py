@@ -179,6 +179,7 @@ SIGNATURES = {
     "lako_headbatch_tn": [C.POINTER(HeadBatch), vp],
     "lako_headbatch_tn_multi": [C.POINTER(HeadBatch), i32, vp],
     "lako_ce_fwd_bwd": [vp, vp, vp, vp, vp, i64, i64, i32, vp],
+    "lako_seq_logprob": [vp, vp, vp, vp, i64, i32, i64, vp],
     "lako_sumsq": [vp, i64, vp, vp],
     "lako_adamw_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, f32, i32, vp],
     "lako_transpose_cast": [vp, vp, i64, i64, i32, vp],

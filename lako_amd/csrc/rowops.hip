@@ -941,6 +941,82 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
   }
 }
 
+// ---- sequence log-probability (candidate scoring) ---------------------------------------------------
+// score[r] = Σ_t log softmax(logits[r, t, :])[labels[r, t]] over the tokens whose label is in [0, V); n_valid[r] their count.
+// One workgroup per sequence walks its T rows in order; a row is read ONCE, 16 bytes per lane and SLP_U loads in flight per lane,
+// with a running (max, Σ exp) per lane that is rescaled when the maximum moves (one extra exp per 4·SLP_U elements); the label's
+// logit is picked out of the same loads.  Lanes → wave (shuffles) → the four waves (LDS, read by thread 0 in wave order) → the
+// sum over t in thread 0: every order is fixed, nothing is atomic, so two launches on the same input agree bit for bit.
+// A row whose label is ignored is not read at all.  The LDS slots alternate with t: one barrier per row.
+constexpr int SLP_U = 8;
+
+__global__ __launch_bounds__(256) void seq_logprob_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                          float* __restrict__ score, int32_t* __restrict__ n_valid, int T, int64_t V) {
+  __shared__ float red[2][3][4];
+  const int64_t r = blockIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float total = 0.f;
+  int cnt = 0, slot = 0;
+  for (int t = 0; t < T; ++t) {
+    const int64_t label = labels[r * T + t];
+    if (label < 0 || label >= V) continue;         // −100, or a caller's error: ignored (the same for every thread of the workgroup)
+    const float* lr = logits + (r * T + t) * V;
+    float m = -INFINITY, s = 0.f, x = 0.f;
+    for (int64_t c0 = threadIdx.x * 4; c0 < V; c0 += 1024 * SLP_U) {
+      f32x4 v[SLP_U];
+#pragma unroll
+      for (int j = 0; j < SLP_U; ++j) {
+        const int64_t c = c0 + 1024 * j;
+        v[j] = c < V ? *reinterpret_cast<const f32x4*>(lr + c) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      }
+      float bm = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < SLP_U; ++j) bm = fmaxf(fmaxf(bm, fmaxf(v[j][0], v[j][1])), fmaxf(v[j][2], v[j][3]));
+      const float nm = fmaxf(m, bm);
+      if (nm > -INFINITY) {
+        float e = 0.f;
+#pragma unroll
+        for (int j = 0; j < SLP_U; ++j) e += __expf(v[j][0] - nm) + __expf(v[j][1] - nm) + __expf(v[j][2] - nm) + __expf(v[j][3] - nm);
+        s = s * __expf(m - nm) + e;
+        m = nm;
+      }
+#pragma unroll
+      for (int j = 0; j < SLP_U; ++j) {
+        const uint64_t k = (uint64_t)(label - (c0 + 1024 * j));
+        if (k < 4) x = k == 0 ? v[j][0] : k == 1 ? v[j][1] : k == 2 ? v[j][2] : v[j][3];
+      }
+    }
+    const float wm = wave_max(m);
+    s = wave_sum(m > -INFINITY ? s * __expf(m - wm) : 0.f);
+    x = wave_sum(x);                               // one lane holds the label's logit, the others 0
+    if (lane == 0) {
+      red[slot][0][wv] = wm;
+      red[slot][1][wv] = s;
+      red[slot][2][wv] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float* rm = red[slot][0];
+      const float* rs = red[slot][1];
+      const float* rx = red[slot][2];
+      const float bm = fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
+      float se = 0.f, xl = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        se += rm[w] > -INFINITY ? rs[w] * __expf(rm[w] - bm) : 0.f;
+        xl += rx[w];
+      }
+      total += xl - (bm + __logf(se));
+      ++cnt;
+    }
+    slot ^= 1;
+  }
+  if (threadIdx.x == 0) {
+    score[r] = total;
+    n_valid[r] = cnt;
+  }
+}
+
 // ---- optimizer ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ out, int det) {
   __shared__ float red[4];
@@ -1448,6 +1524,20 @@ extern "C" int lako_ce_fwd_bwd(const float* logits, const int64_t* labels, float
   hipLaunchKernelGGL(ce_init_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_out, labels, M, sc);
   DISPATCH_T(dtype, hipLaunchKernelGGL((ce_kernel<T>), dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, logits,
                                        labels, loss_out, (T*)dlogits, upstream, V, sc));
+  LAKO_LAUNCH_CHECK();
+  return LAKO_OK;
+}
+
+extern "C" int lako_seq_logprob(const float* logits, const int64_t* labels, float* score, int32_t* n_valid, int64_t R, int T,
+                                int64_t V, lako_stream_t stream) {
+  LAKO_CHECK_ARG(logits && labels && score && n_valid, "lako_seq_logprob: null operand");
+  LAKO_CHECK_ARG(R > 0 && R <= 0x7FFFFFFF && T > 0 && V > 0, "lako_seq_logprob: R=%lld T=%d V=%lld", (long long)R, T, (long long)V);
+  if (V % 4 != 0) {
+    lako_set_error("lako_seq_logprob: V=%lld is not a multiple of 4 (16-byte row loads)", (long long)V);
+    return LAKO_E_ALIGN;
+  }
+  LAKO_CHECK_ALIGN(logits, 16);
+  hipLaunchKernelGGL(seq_logprob_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, logits, labels, score, n_valid, T, V);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }

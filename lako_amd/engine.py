@@ -724,33 +724,40 @@ class Engine:
         r0 = (2 * i + (which == "v")) * inner
         return self.kv_all.g[r0:r0 + inner].unflatten(0, (H, dk))
 
-    def _xattn_buffers(self, ws, B, N, L, T, Ld, Z):
+    def _xattn_buffers(self, ws, B, N, L, T, Ld, Z, keep=True):
         """Workspace of the encoder-state-space cross-attention, sized for the padded batch (the column count of a batch's score
         matrices, xa.ptot, is a prefix of the allocation).  Per decoder layer l and R = T·H query rows per sample:
           dq [B, Ld·2R, d]   rows l·2R … : dC' (written in backward), rows l·2R + R … : Q'          — B operand of the dE product
           ps [Ld·2R, cap]    rows l·2R … : dropout(P),               rows l·2R + R … : dS (backward) — A operand of the dE product
-          s  [Ld, R, cap] fp32 raw scores, st [Ld, B, R, 2] softmax statistics, c [Ld, Z, B, R, d] fp32 C' = P·E in Z key-split slabs"""
+          s  [Ld, R, cap] fp32 raw scores, st [Ld, B, R, 2] softmax statistics, c [Ld, Z, B, R, d] fp32 C' = P·E in Z key-split slabs
+        keep=False (no backward follows: `score`): one layer's worth, which every layer reuses (`slot`)."""
         cfg = self.cfg
         R, d = T * cfg.num_heads, cfg.d_model
         cap = B * (-(-(N * L) // 256) * 256)
-        return dict(R=R, cap=cap, rows=B * N * L,
-                    dq=self._buf(ws, "x.dq", (B, Ld * 2 * R, d)),
-                    ps=self._buf(ws, "x.ps", (Ld * 2 * R, cap)),
-                    s=self._buf(ws, "x.s", (Ld, R, cap), torch.float32),
-                    st=self._buf(ws, "x.st", (Ld, B, R, 2), torch.float32),
-                    c=self._buf(ws, "x.c", (Ld, Z, B, R, d), torch.float32))
+        if not keep:
+            Ld = 1
+        xb = dict(R=R, cap=cap, rows=B * N * L,
+                  dq=self._buf(ws, "x.dq", (B, Ld * 2 * R, d)),
+                  ps=self._buf(ws, "x.ps", (Ld * 2 * R, cap)),
+                  s=self._buf(ws, "x.s", (Ld, R, cap), torch.float32),
+                  st=self._buf(ws, "x.st", (Ld, B, R, 2), torch.float32),
+                  c=self._buf(ws, "x.c", (Ld, Z, B, R, d), torch.float32))
+        if not keep:
+            xb["slot"] = 0
+        return xb
 
     def _xattn_fwd(self, xb, xa, i, qc, enc_out, c2, B, T, max_keys, drop):
         """Cross-attention of decoder layer i in the encoder-state space (see csrc/xattn.hip): qc [B·T, inner] → c2 [B·T, inner]"""
         ops, H, dk, R = self.ops, self.cfg.num_heads, self.cfg.d_kv, xb["R"]
-        qp = xb["dq"][:, (2 * i + 1) * R:(2 * i + 2) * R]
+        j = xb.get("slot", i)        # the layer's buffers (_xattn_buffers: one shared set when nothing is kept)
+        qp = xb["dq"][:, (2 * j + 1) * R:(2 * j + 2) * R]
         ops.headbatch_nt(qc.view(B, T, H, dk), self._xw(i, "k", transposed=True), qp.unflatten(1, (T, H)))
-        s = xb["s"][i][:, xa.p0:xa.p0 + xa.ptot]
+        s = xb["s"][j][:, xa.p0:xa.p0 + xa.ptot]
         ops.xattn_scores(qp, enc_out, xa.k_off, xa.p_off, xa.ptot, s)
-        pr = xb["ps"][2 * i * R:(2 * i + 1) * R, xa.p0:xa.p0 + xa.ptot]
-        ops.xattn_softmax_fwd(s, xb["st"][i], pr, xa.k_off, xa.p_off, T, H, max_keys, drop)
-        ops.xattn_context(pr, enc_out, xa.k_off, xa.p_off, xb["c"][i])
-        ops.headbatch_nt(xb["c"][i].unflatten(2, (T, H)), self._xw(i, "v"), c2.view(B, T, H, dk))
+        pr = xb["ps"][2 * j * R:(2 * j + 1) * R, xa.p0:xa.p0 + xa.ptot]
+        ops.xattn_softmax_fwd(s, xb["st"][j], pr, xa.k_off, xa.p_off, T, H, max_keys, drop)
+        ops.xattn_context(pr, enc_out, xa.k_off, xa.p_off, xb["c"][j])
+        ops.headbatch_nt(xb["c"][j].unflatten(2, (T, H)), self._xw(i, "v"), c2.view(B, T, H, dk))
 
     def _xattn_bwd(self, xb, xa, tmp, i, qc, enc_out, dctx, dqc, B, T, max_keys, drop, b0=0, B_all=None, hb=None):
         """Backward of _xattn_fwd: dctx [B·T, inner] → dqc [B·T, inner], the layer's Wk / Wv gradients, and the rows (dC', dS) the
@@ -862,12 +869,20 @@ class Engine:
             kv = kv[ch["kv_r"][0]:ch["kv_r"][1]]
         return self._heads(kv, ch["kv_b"], ch["kv_t"] if ch["kv_r"] is None else kv.shape[0] // ch["kv_b"], col0)
 
-    def _dec_layer_fwd(self, ws, i, ch, enc_out, kv, rel, T, S):
+    def _dec_layer_fwd(self, ws, i, ch, enc_out, kv, rel, T, S, Tx=None):
         """One decoder block (HF5:448-509) on the rows of one chain: RMSNorm → QKV → causal self-attention → O + residual → RMSNorm →
-        cross-attention query → cross-attention → O + residual → RMSNorm → FFN + residual."""
+        cross-attention query → cross-attention → O + residual → RMSNorm → FFN + residual.
+        `Tx` (default T): the query rows a sample has in the CROSS-attention — `score` hands every sample C sequences of T tokens: the
+        self-attention sees Tx / T causal sequences of length T per sample, the cross-attention (no structure over its query rows)
+        one run of Tx = C·T rows per sample."""
         cfg, ops, lw, dr = self.cfg, self.ops, self.dec[i], ch["dr"]
         d, f, inner, H, eps = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads, cfg.layer_norm_epsilon
         Bc, Ld = ch["B"], cfg.num_decoder_layers
+        Bs, sb0, sb1 = Bc, ch["b0"], ch["b1"]      # the self-attention's sequences: the chain's samples …
+        if Tx is None:
+            Tx = T
+        elif Tx != T:                               # … or Tx / T sequences per sample
+            Bs, sb0, sb1 = Bc * (Tx // T), ch["b0"] * (Tx // T), ch["b1"] * (Tx // T)
         Md = ws[f"d.h{i}"].shape[0]
         R = lambda name, cols, dt=None: self._rows(ws, name, ch, (Md, cols) if cols else (Md,), dt)       # noqa: E731
         h = ws[f"d.h{i}"][ch["r0"]:ch["r1"]]
@@ -884,9 +899,9 @@ class Engine:
             ops.rmsnorm_fwd(h, lw["ln1"].p, xn1, R(f"d.rs1.{i}", 0, torch.float32), eps)
             ops.gemm_nt(xn1, lw["qkv"].w, qkv)
         c1 = R(f"d.ctx.{i}", inner)
-        st = self._buf(ws, f"d.st.{i}", (Md // T, H, T, 4), torch.float32)[ch["b0"]:ch["b1"]]
-        ops.attn_fwd(self._heads(qkv, Bc, T, 0), self._heads(qkv, Bc, T, inner), self._heads(qkv, Bc, T, 2 * inner),
-                     self._heads(c1, Bc, T, 0), st, rel_bias=rel, rel_off=T - 1, causal=True, drop=dr(_dec_site(i, 0)))
+        st = self._buf(ws, f"d.st.{i}", (Md // T, H, T, 4), torch.float32)[sb0:sb1]
+        ops.attn_fwd(self._heads(qkv, Bs, T, 0), self._heads(qkv, Bs, T, inner), self._heads(qkv, Bs, T, 2 * inner),
+                     self._heads(c1, Bs, T, 0), st, rel_bias=rel, rel_off=T - 1, causal=True, drop=dr(_dec_site(i, 0)))
         h1 = R(f"d.h1.{i}", d)
         ops.gemm_nt(c1, lw["o"].w, h1, resid=h, drop=dr(_dec_site(i, 1)))
         xn2 = R(f"d.xn2.{i}", d)
@@ -898,11 +913,11 @@ class Engine:
             ops.gemm_nt(xn2, lw["cq"].w, qc)
         c2 = R(f"d.cctx.{i}", inner)
         if ch["xa"] is not None:
-            self._xattn_fwd(ch["xb"], ch["xa"], i, qc, enc_out, c2, Bc, T, S, dr(_dec_site(i, 2)))
+            self._xattn_fwd(ch["xb"], ch["xa"], i, qc, enc_out, c2, Bc, Tx, S, dr(_dec_site(i, 2)))
         else:
-            cst = self._buf(ws, f"d.cst.{i}", (Md // T, H, T, 4), torch.float32)[ch["b0"]:ch["b1"]]
-            ops.attn_fwd(self._heads(qc, Bc, T, 0), self._cross_kv(kv, ch, 2 * i * inner), self._cross_kv(kv, ch, (2 * i + 1) * inner),
-                         self._heads(c2, Bc, T, 0), cst, drop=dr(_dec_site(i, 2)), **ch["ckw"])
+            cst = self._buf(ws, f"d.cst.{i}", (Md // Tx, H, Tx, 4), torch.float32)[ch["b0"]:ch["b1"]]
+            ops.attn_fwd(self._heads(qc, Bc, Tx, 0), self._cross_kv(kv, ch, 2 * i * inner), self._cross_kv(kv, ch, (2 * i + 1) * inner),
+                         self._heads(c2, Bc, Tx, 0), cst, drop=dr(_dec_site(i, 2)), **ch["ckw"])
         h2 = R(f"d.h2.{i}", d)
         ops.gemm_nt(c2, lw["co"].w, h2, resid=h1, drop=dr(_dec_site(i, 3)))
         xn3 = R(f"d.xn3.{i}", d)
@@ -1076,6 +1091,75 @@ class Engine:
         ops.ce_fwd_bwd(logits, ctx.labels, loss_buf, None)
         self.ctx = ctx
         return loss_buf[0], logits.view(B, T, V)
+
+    # ------------------------------------------------------------------------------------------
+    # candidate scoring
+    # ------------------------------------------------------------------------------------------
+    def score(self, input_ids, attention_mask, candidates, lengths=None, chunk=None):
+        """input_ids / attention_mask [B,N,L], candidates int64 [B,C,T] (−100 = ignore) → (score fp32 [B,C], n_valid int32 [B,C]):
+        score[b,c] = Σ_t log p(candidates[b,c,t] | question b, candidates[b,c,:t]) over the tokens that are not −100, n_valid their count.
+        Eval semantics (no dropout, `step_count` stays).  ONE encoder pass serves all candidates: the cross-attention works on the
+        encoder states and has no structure over its query rows, so sample b simply brings c·T of them (rows ordered [b, c, t]) while
+        the causal self-attention sees B·c sequences of length T.  The candidates go through the decoder `chunk` at a time (default:
+        the largest c with B·c·T <= 4096 rows — the fp32 logits are [B·c·T, V]); each chunk: decoder → LM head → lako_seq_logprob.
+        Touches neither `self.ctx` nor the training workspaces: a call between forward_loss and backward changes nothing there."""
+        cfg, ops = self.cfg, self.ops
+        if cfg.legacy_cross_bias:
+            raise ValueError("score: legacy_cross_bias makes the cross-attention bias depend on the query's position, which the "
+                             "[B, C·T] query layout does not carry")
+        if self.shadows_stale:
+            self.refresh_shadows()
+        B, N, L = input_ids.shape
+        if candidates.dim() != 3 or candidates.shape[0] != B or candidates.dtype != torch.int64 or candidates.numel() == 0:
+            raise ValueError(f"score: candidates must be int64 [B={B}, C, T], got {tuple(candidates.shape)} {candidates.dtype}")
+        C, T = int(candidates.shape[1]), int(candidates.shape[2])
+        d, H, V, Ld, S = cfg.d_model, cfg.num_heads, cfg.vocab_size, cfg.num_decoder_layers, N * L
+        chunk = max(1, min(C, int(chunk) if chunk else 4096 // (B * T)))
+        ws = self._workspace(("score", B, N, L, T, chunk))
+        ids = input_ids.reshape(-1).contiguous()
+        mask_u8 = attention_mask.reshape(B * N, L).to(torch.uint8).contiguous()
+        rag = self._ragged_batch(attention_mask, B, N, L, lengths)
+        self._row_cap = {rag.M: B * N * L} if rag is not None else {}
+        enc_ids = ids if rag is None else self._packed_ids(ws, ids, rag, L)
+        xa = self._xattn_plan(rag, B, N, L, chunk * T * H)
+        self.xattn_active = xa is not None
+        enc_out, kv = self._encode(ws, enc_ids, self._enc_mask(rag, mask_u8), B * N, L, 0.0, 0, save=False, rag=rag, want_kv=xa is None)
+        if rag is None:
+            kb, kt, ckw = B, S, dict(key_mask=mask_u8.view(B, S))
+        else:
+            kb, kt, ckw = 1, rag.M, dict(k_off=rag.soff, max_k=S)
+        rel = self._buf(ws, "d.rel", (H, 2 * T - 1), torch.float32)
+        ops.relpos_expand(self.dec_rel.p, self._lut(T, T, False), rel)
+        score = torch.empty(B, C, dtype=torch.float32, device=self.device)
+        n_valid = torch.empty(B, C, dtype=torch.int32, device=self.device)
+        for c0 in range(0, C, chunk):
+            c = min(chunk, C - c0)
+            wd = ws if c == chunk else ws.setdefault("tail", {})      # the last, smaller chunk: decoder buffers of its own shapes
+            Md, Tx = B * c * T, c * T
+            labels = candidates[:, c0:c0 + c].reshape(B * c, T).contiguous()
+            ops.shift_right(labels, self._buf(wd, "d.ids", (B * c, T), torch.int64))
+            xb = None
+            if xa is not None:
+                if c != chunk:
+                    xa = self._xattn_plan(rag, B, N, L, Tx * H)
+                xb = self._xattn_buffers(wd, B, N, L, Tx, Ld, xa.splits, keep=False)
+            for i in range(Ld + 1):
+                self._buf(wd, f"d.h{i}", (Md, d))
+            dec_out = self._buf(wd, "d.out", (Md, d))
+            self._buf(wd, "d.rsf", (Md,), torch.float32)
+            ch = dict(c=0, b0=0, b1=B, B=B, r0=0, r1=Md, xa=xa, xb=xb, kv_b=kb, kv_t=kt, kv_r=None, ckw=ckw, dr=lambda site: None)
+            for i in range(Ld):
+                self._dec_layer_fwd(wd, i, ch, enc_out, kv, rel, T, S, Tx=Tx)
+            logits = self._buf(wd, "d.logits", (Md, V), torch.float32)
+            ops.gemm_nt(dec_out, self.lm_head.w, logits, alpha=self.head_alpha)
+            if c == C:
+                ops.seq_logprob(logits, labels.view(-1), score.view(-1), n_valid.view(-1), T)
+            else:      # rows [b, c]: the chunk's columns of the [B, C] outputs
+                sc, nv = self._buf(wd, "d.score", (B * c,), torch.float32), self._buf(wd, "d.nvalid", (B * c,), torch.int32)
+                ops.seq_logprob(logits, labels.view(-1), sc, nv, T)
+                score[:, c0:c0 + c].copy_(sc.view(B, c))
+                n_valid[:, c0:c0 + c].copy_(nv.view(B, c))
+        return score, n_valid
 
     # ------------------------------------------------------------------------------------------
     # backward

@@ -226,6 +226,37 @@ class FiDT5(nn.Module):
             return out
         return eng.generate(input_ids, attention_mask, max_length, lengths=passage_lengths)
 
+    @torch.no_grad()
+    def score(self, input_ids, attention_mask, candidates, passage_lengths=None, normalize=False, candidate_chunk=None):
+        """Extension: log-probability of given answers, float32 [B, C] — score[b, c] = Σ_t log p(candidates[b, c, t] | question b,
+        candidates[b, c, :t]) over the tokens that are not −100 (the padding of `labels`); `normalize=True` divides by the number of
+        such tokens (at least 1): the mean token log-probability.  `candidates`: int64 [B, C, T], or [C, T] for one list shared by
+        every question.  Inputs as `forward` takes them ([B,N,L], or [B,N·L] after a 3-D call; attention_mask None = all valid).
+        Eval semantics whatever `.training` says; the encoder runs ONCE for all C candidates, which pass through the decoder
+        `candidate_chunk` at a time (default: as many as keep the fp32 logits at 4096 rows).  The candidate ids are checked once per
+        call — {−100} ∪ [0, vocab_size), else ValueError — which costs one device→host sync."""
+        if input_ids.dim() == 3:
+            self.n_passages = input_ids.size(1)
+        elif self.n_passages is None:
+            raise ValueError("2-D input_ids before any 3-D call: n_passages unknown")
+        B = input_ids.size(0)
+        ids = input_ids.reshape(B, self.n_passages, -1)
+        if attention_mask is None:
+            attention_mask = torch.ones_like(ids, dtype=torch.bool)
+        mask = attention_mask.reshape(B, self.n_passages, -1)
+        cand = torch.as_tensor(candidates)
+        if cand.dim() == 2:
+            cand = cand[None].expand(B, -1, -1)
+        if cand.dim() != 3 or cand.size(0) != B or cand.dtype != torch.int64 or cand.numel() == 0:
+            raise ValueError(f"candidates must be int64 [B, C, T] or [C, T], got {tuple(cand.shape)} {cand.dtype}")
+        cand = cand.to(ids.device)
+        if bool((((cand < 0) & (cand != -100)) | (cand >= self.config.vocab_size)).any()):
+            raise ValueError(f"candidates hold ids outside [0, {self.config.vocab_size}) that are not -100")
+        score, n_valid = self._get_engine().score(ids, mask, cand, lengths=passage_lengths, chunk=candidate_chunk)
+        if normalize:
+            score = score / n_valid.clamp(min=1)
+        return score
+
     def set_checkpoint(self, use_checkpoint):
         """src/model.py:84-90: recompute each encoder block in backward from its saved input instead of keeping its
         intermediates (the reference's CheckpointWrapper + torch.utils.checkpoint, :237-283).  With 288 GB of HBM per

@@ -683,6 +683,18 @@ class HipOps:
         self._timed("ce_fwd_bwd", 0.0, lambda: check(self.lib.lako_ce_fwd_bwd(_p(logits), _p(labels), _p(loss_out), _p(dlogits), _p(upstream), M, V,
                                        _dt(dlogits) if dlogits is not None else LAKO_F32, self._stream()), "lako_ce_fwd_bwd"))
 
+    def seq_logprob(self, logits, labels, score, n_valid, T):
+        """score fp32 [R] = Σ_t log softmax(logits[r·T + t])[labels[r·T + t]] over the labels that are not −100, n_valid int32 [R] their
+        count: logits fp32 [R·T, V] contiguous, labels int64 [R·T] (lako_seq_logprob)"""
+        M, V = logits.shape
+        R = M // T
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or labels.dtype != torch.int64 or not labels.is_contiguous() or \
+                R * T != M or labels.numel() != M or score.dtype != torch.float32 or n_valid.dtype != torch.int32 or \
+                score.numel() != R or n_valid.numel() != R or not score.is_contiguous() or not n_valid.is_contiguous():
+            raise LakoError("seq_logprob: logits fp32 [R·T, V], labels int64 [R·T], score fp32 [R], n_valid int32 [R], all contiguous")
+        self._timed("seq_logprob", 0.0, lambda: check(self.lib.lako_seq_logprob(_p(logits), _p(labels), _p(score), _p(n_valid), R, int(T), V,
+                                                                                self._stream()), "lako_seq_logprob"))
+
     def sumsq(self, g, out):
         self._timed("sumsq", 0.0, lambda: check(self.lib.lako_sumsq(_p(g), g.numel(), _p(out), self._stream()), "lako_sumsq"))
 
