@@ -438,7 +438,8 @@ int lako_xattn_context(const void* p, int64_t p_ld, const void* e, int64_t e_ld,
 /* row r = t*H + h of sample b: stats[b][r] = (max, 1 / sum exp); p = dropout(softmax) as bf16, zeros in the padding columns.
  * Dropout: the attention block recipe of lako_attn_fwd with bh = b*H + h, q = t, k = key index in the sample, Lq = T,
  * Lk = max_keys (so that both formulations of the cross-attention drop the same probabilities); max_keys must be at least
- * every sample's key count (rows of up to 8 192 keys are processed from registers). */
+ * every sample's key count — a caller contract, not checked: the kernels are chosen by max_keys, and a longer sample is cut off at
+ * what its kernel holds (rows of up to 8 192 keys are processed from registers).  Every sample has at least one key. */
 int lako_xattn_softmax_fwd(const float* s, int64_t s_ld, float* stats, void* p, int64_t p_ld, const int32_t* k_off,
                            const int32_t* p_off, int B, int T, int H, int max_keys, lako_dropout_t drop, lako_stream_t stream);
 /* ds = P∘(dropout_bwd(dp) − Σ_keys dropout(P)·dp) as bf16 (P recomputed from s and stats) */
@@ -477,6 +478,41 @@ int lako_headbatch_tn(const lako_headbatch_t* p, lako_stream_t stream);
 /* (round 4) n <= 24 lako_headbatch_tn problems of one N, H and b_dtype in ONE launch — the Wk / Wv gradients of all decoder layers,
  * deferred to the end of the decoder's backward (each alone is nothing but its dispatch). */
 int lako_headbatch_tn_multi(const lako_headbatch_t* items, int n, lako_stream_t stream);
+
+/* ---- plan queries (as for the GEMMs and the attention above): WHICH kernel the three cross-attention entries that choose between
+ * kernels would launch, and with what, without launching.  Same contract: the arguments of the launching entry point (the softmax query
+ * serves both directions: bwd = 0 takes lako_xattn_softmax_fwd's arguments and ignores dp, bwd != 0 lako_xattn_softmax_bwd's with p = ds),
+ * the same validation and refusal codes, the very plan the launching call consumes, no HIP call (they run on a host without a GPU),
+ * `out` zeroed on refusal.  (lako_xattn_scores / _context / _decode_combine / lako_headbatch_tn have one kernel each.) */
+enum {
+  LAKO_XK_NONE = 0,
+  LAKO_XK_SOFTMAX_REG = 1, /* xsoftmax_reg_kernel<bwd, nv>: a padded segment of at most 1024 * nv columns, held in registers */
+  LAKO_XK_SOFTMAX = 2,     /* xsoftmax_kernel<bwd>: any length, the row is read once per pass */
+  LAKO_XK_HB_CONTRACT = 3, /* hb_contract_kernel<af32, ks>: N = 64, K = 128 * ks in {512, 768, 1024} */
+  LAKO_XK_HB_NT = 4,       /* hb_nt_kernel<af32, nt, ku>: every other head-batched NT product */
+  LAKO_XK_DECODE = 5       /* xdecode_kernel<ks>: D = 256 * ks, a ring of `stages` LDS stages */
+};
+typedef struct {
+  int32_t kernel; /* LAKO_XK_* */
+  /* which instantiation of it */
+  int32_t bwd;    /* softmax: the backward instantiation */
+  int32_t nv;     /* LAKO_XK_SOFTMAX_REG: 16-byte vectors per thread, 4 | 8 */
+  int32_t af32;   /* head-batched products: A is fp32 (key-split slabs summed on the way in) */
+  int32_t nt;     /* LAKO_XK_HB_NT: 16-column tiles per wave, 4 | 1 */
+  int32_t ku;     /* LAKO_XK_HB_NT: K-steps of 32 loaded together, 8 | 2 | 1 */
+  int32_t ks;     /* LAKO_XK_HB_CONTRACT: K-steps of 32 per wave (K / 128); LAKO_XK_DECODE: K-steps per wave (D / 256) */
+  int32_t stages; /* LAKO_XK_DECODE: stages of the LDS ring, 3 | 2 */
+  /* the launch */
+  int32_t gx, gy, gz; /* grid, in workgroups */
+  int32_t block;      /* threads per workgroup */
+  int32_t lds;        /* dynamic LDS bytes */
+} lako_xattn_plan_t;
+int lako_xattn_softmax_plan(int bwd, const float* s, const float* dp, int64_t s_ld, const float* stats, void* p, int64_t p_ld,
+                            const int32_t* k_off, const int32_t* p_off, int B, int T, int H, int max_keys, lako_dropout_t drop,
+                            lako_xattn_plan_t* out);
+int lako_headbatch_nt_plan(const lako_headbatch_t* p, lako_xattn_plan_t* out);
+int lako_xattn_decode_plan(const void* q, int64_t q_sb, int64_t q_ld, const void* e, int64_t e_ld, const int32_t* k_off,
+                           float* part_ml, float* part_c, int R, int D, int B, int key_splits, lako_xattn_plan_t* out);
 
 /* ---- LM-head loss (HF5:1051-1054): CrossEntropyLoss(ignore_index=-100), mean over valid labels ----
  * logits fp32 [M, V]; loss_out[0] = mean loss, loss_out[1] = number of valid labels;

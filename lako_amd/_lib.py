@@ -132,6 +132,18 @@ class AttnPlan(C.Structure):
  ATTN_ENC_BWD_DKV, ATTN_ENC_BWD_DKV_P, ATTN_ENC_BWD_FUSED) = range(12)
 
 
+class XattnPlan(C.Structure):
+    """lako_xattn_plan_t: what lako_xattn_softmax_plan / lako_headbatch_nt_plan / lako_xattn_decode_plan say the launching call would run"""
+    _fields_ = [(n, i32) for n in ("kernel", "bwd", "nv", "af32", "nt", "ku", "ks", "stages", "gx", "gy", "gz", "block", "lds")]
+
+    def __repr__(self):
+        return "XattnPlan(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_ if getattr(self, n) or n == "kernel") + ")"
+
+
+# lako_xattn_plan_t.kernel (include/lako_hip.h LAKO_XK_*)
+XK_NONE, XK_SOFTMAX_REG, XK_SOFTMAX, XK_HB_CONTRACT, XK_HB_NT, XK_DECODE = range(6)
+
+
 # name -> argtypes (restype is always int).  Must list EVERY function include/lako_hip.h declares:
 # tests/test_abi.py cross-checks this table against the header and the .so's dynamic symbols.
 SIGNATURES = {
@@ -174,8 +186,11 @@ SIGNATURES = {
     "lako_xattn_softmax_fwd": [vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, i32, Dropout, vp],
     "lako_xattn_softmax_bwd": [vp, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, i32, Dropout, vp],
     "lako_xattn_decode": [vp, i64, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp],
+    "lako_xattn_decode_plan": [vp, i64, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(XattnPlan)],
     "lako_xattn_decode_combine": [vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "lako_xattn_softmax_plan": [i32, vp, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, i32, Dropout, C.POINTER(XattnPlan)],
     "lako_headbatch_nt": [C.POINTER(HeadBatch), vp],
+    "lako_headbatch_nt_plan": [C.POINTER(HeadBatch), C.POINTER(XattnPlan)],
     "lako_headbatch_tn": [C.POINTER(HeadBatch), vp],
     "lako_headbatch_tn_multi": [C.POINTER(HeadBatch), i32, vp],
     "lako_ce_fwd_bwd": [vp, vp, vp, vp, vp, i64, i64, i32, vp],

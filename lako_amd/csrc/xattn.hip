@@ -952,6 +952,20 @@ extern "C" int lako_xattn_context(const void* p, int64_t p_ld, const void* e, in
   return LAKO_OK;
 }
 
+// --------------------------------------------------------------------------------------------------------------------
+// Host dispatch of the three entries that choose between kernels: decide, then launch.  Each *_decide runs the entry's whole
+// validation, fills the kernel arguments and the plan (lako_xattn_plan_t) from ONE statement of the rule, and makes no HIP call;
+// the launching entry runs the plan, the plan query (lako_xattn_softmax_plan / lako_headbatch_nt_plan / lako_xattn_decode_plan)
+// returns it.  Messages name the launching entry.  A refusal leaves the plan zeroed.
+// --------------------------------------------------------------------------------------------------------------------
+#define XCHECK_ALIGN(fn, ptr, a)                                                          \
+  do {                                                                                    \
+    if ((reinterpret_cast<uintptr_t>(ptr) % (a)) != 0) {                                  \
+      lako_set_error("%s: pointer %s not %d-byte aligned", fn, #ptr, (int)(a));           \
+      return LAKO_E_ALIGN;                                                                \
+    }                                                                                     \
+  } while (0)
+
 static int xsoftmax_args(const char* fn, SmArgs& a, const float* s, int64_t s_ld, float* stats, void* p, int64_t p_ld,
                          const int32_t* k_off, const int32_t* p_off, int B, int T, int H, int max_keys, lako_dropout_t drop) {
   if (!s || !stats || !p || !k_off || !p_off || B <= 0 || T <= 0 || H <= 0 || max_keys <= 0 || s_ld % 4 != 0 || p_ld % 4 != 0) {
@@ -976,19 +990,55 @@ static int xsoftmax_args(const char* fn, SmArgs& a, const float* s, int64_t s_ld
   return LAKO_OK;
 }
 
+// The softmax rule: no sample's padded segment is longer than max_keys rounded up to 256 columns; a segment of at most 1024·NV columns
+// is held in NV 16-byte vectors per thread (xsoftmax_reg_kernel, NV 4 | 8), longer ones take the kernel that re-reads the row.
+static lako_xattn_plan_t xsoftmax_plan(bool bwd, int B, int T, int H, int max_keys) {
+  lako_xattn_plan_t pl{};
+  const int seg = (max_keys + 255) / 256 * 256;
+  pl.nv = seg <= 4096 ? 4 : seg <= 8192 ? 8 : 0;
+  pl.kernel = pl.nv ? LAKO_XK_SOFTMAX_REG : LAKO_XK_SOFTMAX;
+  pl.bwd = bwd ? 1 : 0;
+  pl.gx = T * H; pl.gy = B; pl.gz = 1;
+  pl.block = 256;
+  return pl;
+}
+
+static int xsoftmax_decide(bool bwd, const float* s, const float* dp, int64_t s_ld, float* stats, void* p, int64_t p_ld,
+                           const int32_t* k_off, const int32_t* p_off, int B, int T, int H, int max_keys, lako_dropout_t drop,
+                           SmArgs& a, lako_xattn_plan_t& pl) {
+  const char* fn = bwd ? "lako_xattn_softmax_bwd" : "lako_xattn_softmax_fwd";
+  pl = lako_xattn_plan_t{};
+  a = SmArgs{};
+  if (const int rc = xsoftmax_args(fn, a, s, s_ld, stats, p, p_ld, k_off, p_off, B, T, H, max_keys, drop)) return rc;
+  if (bwd) LAKO_CHECK_ARG(dp != nullptr, "%s: null dp", fn);
+  XCHECK_ALIGN(fn, s, 16);
+  if (bwd) XCHECK_ALIGN(fn, dp, 16);
+  XCHECK_ALIGN(fn, p, 8);
+  a.dp = bwd ? dp : nullptr;
+  pl = xsoftmax_plan(bwd, B, T, H, max_keys);
+  return LAKO_OK;
+}
+
+static void xsoftmax_run(const lako_xattn_plan_t& pl, const SmArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy), block((unsigned)pl.block);
+#define XSM_GO(BWD)                                                                                                       \
+  do {                                                                                                                    \
+    if (pl.nv == 4) hipLaunchKernelGGL((xsoftmax_reg_kernel<BWD, 4>), grid, block, 0, s, a);                              \
+    else if (pl.nv == 8) hipLaunchKernelGGL((xsoftmax_reg_kernel<BWD, 8>), grid, block, 0, s, a);                         \
+    else hipLaunchKernelGGL((xsoftmax_kernel<BWD>), grid, block, 0, s, a);                                                \
+  } while (0)
+  if (!pl.bwd) XSM_GO(false);
+  else XSM_GO(true);
+#undef XSM_GO
+}
+
 extern "C" int lako_xattn_softmax_fwd(const float* s, int64_t s_ld, float* stats, void* p, int64_t p_ld, const int32_t* k_off,
                                       const int32_t* p_off, int B, int T, int H, int max_keys, lako_dropout_t drop,
                                       lako_stream_t stream) {
-  SmArgs a{};
-  int rc = xsoftmax_args("lako_xattn_softmax_fwd", a, s, s_ld, stats, p, p_ld, k_off, p_off, B, T, H, max_keys, drop);
-  if (rc) return rc;
-  LAKO_CHECK_ALIGN(s, 16);
-  LAKO_CHECK_ALIGN(p, 8);
-  const dim3 grid((unsigned)(T * H), (unsigned)B);
-  const int seg = (max_keys + 255) / 256 * 256;     // no sample's padded segment is longer
-  if (seg <= 4096) hipLaunchKernelGGL((xsoftmax_reg_kernel<false, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else if (seg <= 8192) hipLaunchKernelGGL((xsoftmax_reg_kernel<false, 8>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((xsoftmax_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  SmArgs a;
+  lako_xattn_plan_t pl;
+  if (const int rc = xsoftmax_decide(false, s, nullptr, s_ld, stats, p, p_ld, k_off, p_off, B, T, H, max_keys, drop, a, pl)) return rc;
+  xsoftmax_run(pl, a, (hipStream_t)stream);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }
@@ -996,69 +1046,106 @@ extern "C" int lako_xattn_softmax_fwd(const float* s, int64_t s_ld, float* stats
 extern "C" int lako_xattn_softmax_bwd(const float* s, const float* dp, int64_t s_ld, const float* stats, void* ds, int64_t p_ld,
                                       const int32_t* k_off, const int32_t* p_off, int B, int T, int H, int max_keys,
                                       lako_dropout_t drop, lako_stream_t stream) {
-  SmArgs a{};
-  int rc = xsoftmax_args("lako_xattn_softmax_bwd", a, s, s_ld, const_cast<float*>(stats), ds, p_ld, k_off, p_off, B, T, H,
-                         max_keys, drop);
-  if (rc) return rc;
-  LAKO_CHECK_ARG(dp != nullptr, "lako_xattn_softmax_bwd: null dp");
-  LAKO_CHECK_ALIGN(s, 16);
-  LAKO_CHECK_ALIGN(dp, 16);
-  LAKO_CHECK_ALIGN(ds, 8);
-  a.dp = dp;
-  const dim3 grid((unsigned)(T * H), (unsigned)B);
-  const int seg = (max_keys + 255) / 256 * 256;
-  if (seg <= 4096) hipLaunchKernelGGL((xsoftmax_reg_kernel<true, 4>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else if (seg <= 8192) hipLaunchKernelGGL((xsoftmax_reg_kernel<true, 8>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((xsoftmax_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  SmArgs a;
+  lako_xattn_plan_t pl;
+  if (const int rc = xsoftmax_decide(true, s, dp, s_ld, const_cast<float*>(stats), ds, p_ld, k_off, p_off, B, T, H, max_keys, drop, a, pl))
+    return rc;
+  xsoftmax_run(pl, a, (hipStream_t)stream);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }
 
-extern "C" int lako_headbatch_nt(const lako_headbatch_t* p, lako_stream_t stream) {
-  LAKO_CHECK_ARG(p && p->a && p->b && p->c, "lako_headbatch_nt: null operand");
+extern "C" int lako_xattn_softmax_plan(int bwd, const float* s, const float* dp, int64_t s_ld, const float* stats, void* p,
+                                       int64_t p_ld, const int32_t* k_off, const int32_t* p_off, int B, int T, int H, int max_keys,
+                                       lako_dropout_t drop, lako_xattn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_xattn_softmax_plan: null out");
+  SmArgs a;
+  return xsoftmax_decide(bwd != 0, s, dp, s_ld, const_cast<float*>(stats), p, p_ld, k_off, p_off, B, T, H, max_keys, drop, a, *out);
+}
+
+// The lako_headbatch_nt rule.
+//   "contract" (N = 64 columns per head, K = d_model in {512, 768, 1024}): hb_contract_kernel<AF32, KS = K / 128>, one workgroup per
+//       16 × 16 output tile, its four waves a quarter of K each;
+//   everything else: hb_nt_kernel<AF32, NT, KU>, one wave per 16 × (16·NT) tile — NT = 4 when N is a multiple of 64 above 64 ("expand":
+//       N = d_model), else 1; KU K-steps of 32 loaded together: 2 | 1 (K % 64) when NT = 4, 8 | 1 (K % 256) when NT = 1.
+static lako_xattn_plan_t hb_nt_plan(int M, int N, int K, int H, bool f32) {
+  lako_xattn_plan_t pl{};
+  pl.af32 = f32 ? 1 : 0;
+  pl.block = 256;
+  const int tiles_m = (M + 15) / 16;
+  if (N == 64 && (K == 512 || K == 768 || K == 1024)) {
+    pl.kernel = LAKO_XK_HB_CONTRACT;
+    pl.ks = K / 128;
+    pl.gx = tiles_m; pl.gy = H; pl.gz = 4;
+    return pl;
+  }
+  pl.kernel = LAKO_XK_HB_NT;
+  pl.nt = N % 64 == 0 && N > 64 ? 4 : 1;
+  pl.ku = pl.nt == 4 ? (K % 64 == 0 ? 2 : 1) : (K % 256 == 0 ? 8 : 1);
+  const int waves = tiles_m * (N / (16 * pl.nt)) * H;
+  pl.gx = (waves + 3) / 4; pl.gy = 1; pl.gz = 1;
+  return pl;
+}
+
+static int hb_nt_decide(const lako_headbatch_t* p, HbArgs& a, lako_xattn_plan_t& pl) {
+  const char* fn = "lako_headbatch_nt";
+  pl = lako_xattn_plan_t{};
+  LAKO_CHECK_ARG(p && p->a && p->b && p->c, "%s: null operand", fn);
   LAKO_CHECK_ARG(p->M > 0 && p->T > 0 && p->H > 0 && p->K > 0 && p->K % 32 == 0 && p->N > 0 && p->N % 16 == 0,
-                 "lako_headbatch_nt: M, T, H > 0, K %% 32 == 0, N %% 16 == 0 (N=%d K=%d)", p->N, p->K);
-  LAKO_CHECK_ARG((p->a_dtype == LAKO_BF16 || p->a_dtype == LAKO_F32) && p->b_dtype == LAKO_BF16, "lako_headbatch_nt: dtypes");
+                 "%s: M, T, H > 0, K %% 32 == 0, N %% 16 == 0 (N=%d K=%d)", fn, p->N, p->K);
+  LAKO_CHECK_ARG((p->a_dtype == LAKO_BF16 || p->a_dtype == LAKO_F32) && p->b_dtype == LAKO_BF16, "%s: dtypes", fn);
   LAKO_CHECK_ARG(p->a_sb % 8 == 0 && p->a_st % 8 == 0 && p->a_sh % 8 == 0 && p->b_sh % 8 == 0 && p->ldb % 8 == 0 &&
                      p->c_sb % 4 == 0 && p->c_st % 4 == 0 && p->c_sh % 4 == 0,
-                 "lako_headbatch_nt: operand strides must keep 16-byte (A, B) / 8-byte (C) alignment");
-  LAKO_CHECK_ALIGN(p->a, 16);
-  LAKO_CHECK_ALIGN(p->b, 16);
-  LAKO_CHECK_ALIGN(p->c, 8);
-  HbArgs a{};
+                 "%s: operand strides must keep 16-byte (A, B) / 8-byte (C) alignment", fn);
+  XCHECK_ALIGN(fn, p->a, 16);
+  XCHECK_ALIGN(fn, p->b, 16);
+  XCHECK_ALIGN(fn, p->c, 8);
+  a = HbArgs{};
   a.A = (const char*)p->a; a.a_sb = p->a_sb; a.a_st = p->a_st; a.a_sh = p->a_sh;
   a.B = (const char*)p->b; a.b_sh = p->b_sh; a.ldb = p->ldb;
   a.C = (char*)p->c; a.c_sb = p->c_sb; a.c_st = p->c_st; a.c_sh = p->c_sh;
   a.M = p->M; a.T = p->T; a.N = p->N; a.K = p->K; a.H = p->H;
   a.n_slabs = p->n_slabs > 0 ? p->n_slabs : 1; a.slab_stride = p->slab_stride;
-  LAKO_CHECK_ARG(a.n_slabs == 1 || (p->a_dtype == LAKO_F32 && p->slab_stride % 4 == 0), "lako_headbatch_nt: slabs need an fp32 A");
-  const bool f32 = p->a_dtype == LAKO_F32;
-  hipStream_t s = (hipStream_t)stream;
-  if (p->N == 64 && p->K % 128 == 0 && (p->K == 512 || p->K == 768 || p->K == 1024)) {
-    const dim3 grid((unsigned)((p->M + 15) / 16), (unsigned)p->H, 4);
-#define HC_GO(F32, KSV) hipLaunchKernelGGL((hb_contract_kernel<F32, KSV>), grid, dim3(256), 0, s, a)
-    if (p->K == 512) { if (f32) HC_GO(true, 4); else HC_GO(false, 4); }
-    else if (p->K == 768) { if (f32) HC_GO(true, 6); else HC_GO(false, 6); }
+  LAKO_CHECK_ARG(a.n_slabs == 1 || (p->a_dtype == LAKO_F32 && p->slab_stride % 4 == 0), "%s: slabs need an fp32 A", fn);
+  pl = hb_nt_plan(p->M, p->N, p->K, p->H, p->a_dtype == LAKO_F32);
+  return LAKO_OK;
+}
+
+static void hb_nt_run(const lako_xattn_plan_t& pl, const HbArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy, (unsigned)pl.gz), block((unsigned)pl.block);
+  const bool f32 = pl.af32 != 0;
+  if (pl.kernel == LAKO_XK_HB_CONTRACT) {
+#define HC_GO(F32, KSV) hipLaunchKernelGGL((hb_contract_kernel<F32, KSV>), grid, block, 0, s, a)
+    if (pl.ks == 4) { if (f32) HC_GO(true, 4); else HC_GO(false, 4); }
+    else if (pl.ks == 6) { if (f32) HC_GO(true, 6); else HC_GO(false, 6); }
     else { if (f32) HC_GO(true, 8); else HC_GO(false, 8); }
 #undef HC_GO
-    LAKO_LAUNCH_CHECK();
-    return LAKO_OK;
+    return;
   }
-  const int nt = p->N % 64 == 0 && p->N > 64 ? 4 : 1;
-  const int ku = nt == 4 ? (p->K % 64 == 0 ? 2 : 1) : (p->K % 256 == 0 ? 8 : 1);
-  const int waves = ((p->M + 15) / 16) * (p->N / (16 * nt)) * p->H;
-  const dim3 grid((unsigned)((waves + 3) / 4));
-#define HB_GO(F32, NTV, KUV) hipLaunchKernelGGL((hb_nt_kernel<F32, NTV, KUV>), grid, dim3(256), 0, s, a)
-  if (nt == 4) {
-    if (ku == 2) { if (f32) HB_GO(true, 4, 2); else HB_GO(false, 4, 2); }
+#define HB_GO(F32, NTV, KUV) hipLaunchKernelGGL((hb_nt_kernel<F32, NTV, KUV>), grid, block, 0, s, a)
+  if (pl.nt == 4) {
+    if (pl.ku == 2) { if (f32) HB_GO(true, 4, 2); else HB_GO(false, 4, 2); }
     else { if (f32) HB_GO(true, 4, 1); else HB_GO(false, 4, 1); }
   } else {
-    if (ku == 8) { if (f32) HB_GO(true, 1, 8); else HB_GO(false, 1, 8); }
+    if (pl.ku == 8) { if (f32) HB_GO(true, 1, 8); else HB_GO(false, 1, 8); }
     else { if (f32) HB_GO(true, 1, 1); else HB_GO(false, 1, 1); }
   }
 #undef HB_GO
+}
+
+extern "C" int lako_headbatch_nt(const lako_headbatch_t* p, lako_stream_t stream) {
+  HbArgs a;
+  lako_xattn_plan_t pl;
+  if (const int rc = hb_nt_decide(p, a, pl)) return rc;
+  hb_nt_run(pl, a, (hipStream_t)stream);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
+}
+
+extern "C" int lako_headbatch_nt_plan(const lako_headbatch_t* p, lako_xattn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_headbatch_nt_plan: null out");
+  HbArgs a;
+  return hb_nt_decide(p, a, *out);
 }
 
 static int hb_tn_args(const lako_headbatch_t* p, HbArgs& a);
@@ -1111,36 +1198,66 @@ static int hb_tn_args(const lako_headbatch_t* p, HbArgs& a) {
   return LAKO_OK;
 }
 
-extern "C" int lako_xattn_decode(const void* q, int64_t q_sb, int64_t q_ld, const void* e, int64_t e_ld, const int32_t* k_off,
-                                 float* part_ml, float* part_c, int R, int D, int B, int key_splits, lako_stream_t stream) {
-  LAKO_CHECK_ARG(q && e && k_off && part_ml && part_c, "lako_xattn_decode: null operand");
+// The decode rule: xdecode_kernel<KS = D / 256>; its ring holds three [32 keys × D] stages next to the 16 KiB of partial score tiles
+// when that fits 160 KiB of LDS (D = 512, 768), else two (D = 1024) — the kernel derives the same count from D.
+static lako_xattn_plan_t xdecode_plan(int D, int B, int key_splits) {
+  lako_xattn_plan_t pl{};
+  const int stage_b = 32 * D * 2, red_b = 8 * 32 * 16 * 4;
+  pl.kernel = LAKO_XK_DECODE;
+  pl.ks = D / 256;
+  pl.stages = 3 * stage_b + red_b <= 160 * 1024 ? 3 : 2;
+  pl.lds = pl.stages * stage_b + red_b;
+  pl.gx = key_splits; pl.gy = B; pl.gz = 1;
+  pl.block = 512;
+  return pl;
+}
+
+static int xdecode_decide(const void* q, int64_t q_sb, int64_t q_ld, const void* e, int64_t e_ld, const int32_t* k_off, float* part_ml,
+                          float* part_c, int R, int D, int B, int key_splits, XdArgs& a, lako_xattn_plan_t& pl) {
+  const char* fn = "lako_xattn_decode";
+  pl = lako_xattn_plan_t{};
+  LAKO_CHECK_ARG(q && e && k_off && part_ml && part_c, "%s: null operand", fn);
   LAKO_CHECK_ARG(R >= 1 && R <= 16 && (D == 512 || D == 768 || D == 1024) && B >= 1 && key_splits >= 1 && key_splits <= 64 &&
                      e_ld % 8 == 0 && e_ld >= D && e_ld < (1 << 20) && q_ld % 8 == 0 && q_sb % 8 == 0,
-                 "lako_xattn_decode: R <= 16, D in {512, 768, 1024}, 1 <= key_splits <= 64, 16-byte rows (R=%d D=%d)", R, D);
-  LAKO_CHECK_ALIGN(q, 16);
-  LAKO_CHECK_ALIGN(e, 16);
-  LAKO_CHECK_ALIGN(part_c, 16);
-  XdArgs a{};
+                 "%s: R <= 16, D in {512, 768, 1024}, 1 <= key_splits <= 64, 16-byte rows (R=%d D=%d)", fn, R, D);
+  XCHECK_ALIGN(fn, q, 16);
+  XCHECK_ALIGN(fn, e, 16);
+  XCHECK_ALIGN(fn, part_c, 16);
+  a = XdArgs{};
   a.q = (const char*)q; a.q_sb = q_sb; a.q_ld = q_ld;
   a.e = (const char*)e; a.e_ld = e_ld; a.k_off = k_off;
   a.part_ml = part_ml; a.part_c = part_c;
   a.R = R; a.D = D; a.B = B; a.Z = key_splits;
-  const int stage_b = 32 * D * 2, red_b = 8 * 32 * 16 * 4;
-  const int lds = (3 * stage_b + red_b <= 160 * 1024 ? 3 : 2) * stage_b + red_b;
-  const dim3 grid((unsigned)key_splits, (unsigned)B);
+  pl = xdecode_plan(D, B, key_splits);
+  return LAKO_OK;
+}
+
+extern "C" int lako_xattn_decode(const void* q, int64_t q_sb, int64_t q_ld, const void* e, int64_t e_ld, const int32_t* k_off,
+                                 float* part_ml, float* part_c, int R, int D, int B, int key_splits, lako_stream_t stream) {
+  XdArgs a;
+  lako_xattn_plan_t pl;
+  if (const int rc = xdecode_decide(q, q_sb, q_ld, e, e_ld, k_off, part_ml, part_c, R, D, B, key_splits, a, pl)) return rc;
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy), block((unsigned)pl.block);
   hipStream_t s = (hipStream_t)stream;
 #define XD_GO(KSV)                                                                                                     \
   do {                                                                                                                 \
     static lako_lds_cur_t done;                                                                                          \
-    xset_lds(reinterpret_cast<const void*>(&xdecode_kernel<KSV>), lds, done);                                          \
-    hipLaunchKernelGGL((xdecode_kernel<KSV>), grid, dim3(512), lds, s, a);                                             \
+    xset_lds(reinterpret_cast<const void*>(&xdecode_kernel<KSV>), pl.lds, done);                                       \
+    hipLaunchKernelGGL((xdecode_kernel<KSV>), grid, block, pl.lds, s, a);                                              \
   } while (0)
-  if (D == 512) XD_GO(2);
-  else if (D == 768) XD_GO(3);
+  if (pl.ks == 2) XD_GO(2);
+  else if (pl.ks == 3) XD_GO(3);
   else XD_GO(4);
 #undef XD_GO
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
+}
+
+extern "C" int lako_xattn_decode_plan(const void* q, int64_t q_sb, int64_t q_ld, const void* e, int64_t e_ld, const int32_t* k_off,
+                                      float* part_ml, float* part_c, int R, int D, int B, int key_splits, lako_xattn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_xattn_decode_plan: null out");
+  XdArgs a;
+  return xdecode_decide(q, q_sb, q_ld, e, e_ld, k_off, part_ml, part_c, R, D, B, key_splits, a, *out);
 }
 
 extern "C" int lako_xattn_decode_combine(const float* part_ml, const float* part_c, const void* wv, int64_t ldw, void* ctx,

@@ -561,8 +561,8 @@ class HipOps:
             raise LakoError(f"{name}: expected a [B, T, H, X] view with a contiguous last dim, got {tuple(t.shape)} / {t.stride()}")
         return t.stride(0), t.stride(1), t.stride(2)
 
-    def headbatch_nt(self, A, Bw, Cm):
-        """Cm[b,t,h,n] = Σ_k A[b,t,h,k]·Bw[h,n,k]:  A [B,T,H,K] bf16|fp32, Bw [H,N,K] bf16, Cm [B,T,H,N] bf16 (strided views)"""
+    def _hb_nt_struct(self, A, Bw, Cm):
+        """the lako_headbatch_t of a call: what headbatch_nt launches and headbatch_nt_plan asks about"""
         from ._lib import HeadBatch
         slabs, slab_stride = 1, 0
         if A.dim() == 5:      # [Z, B, T, H, K] fp32: the key-split slabs of xattn_context, added in order
@@ -579,7 +579,20 @@ class HipOps:
         hb.M, hb.T, hb.H, hb.N, hb.K = Bz * T, T, H, N, K
         hb.a_dtype, hb.b_dtype = _dt(A), _dt(Bw)
         hb.n_slabs, hb.slab_stride = slabs, slab_stride
-        self._timed("headbatch", 2.0 * Bz * T * H * N * K, lambda: check(self.lib.lako_headbatch_nt(hb, self._stream()), "lako_headbatch_nt"))
+        return hb, 2.0 * Bz * T * H * N * K
+
+    def headbatch_nt(self, A, Bw, Cm):
+        """Cm[b,t,h,n] = Σ_k A[b,t,h,k]·Bw[h,n,k]:  A [B,T,H,K] bf16|fp32, Bw [H,N,K] bf16, Cm [B,T,H,N] bf16 (strided views)"""
+        hb, flops = self._hb_nt_struct(A, Bw, Cm)
+        self._timed("headbatch", flops, lambda: check(self.lib.lako_headbatch_nt(hb, self._stream()), "lako_headbatch_nt"))
+
+    def headbatch_nt_plan(self, A, Bw, Cm):
+        """the launch headbatch_nt would make for these arguments (lako_headbatch_nt_plan: the same struct, nothing launched)"""
+        from ._lib import XattnPlan
+        hb, _ = self._hb_nt_struct(A, Bw, Cm)
+        plan = XattnPlan()
+        check(self.lib.lako_headbatch_nt_plan(hb, C.byref(plan)), "lako_headbatch_nt_plan")
+        return plan
 
     def headbatch_tn(self, A, Bm, Cw):
         """Cw[h,j,c] += Σ_{b,t} A[b,t,h,j]·Bm[b,t,h,c]:  A [B,T,H,64] bf16, Bm [B,T,H,N] bf16|fp32, Cw [H,64,N] fp32 (views)"""
@@ -641,17 +654,29 @@ class HipOps:
     def xattn_decode_ok(H, d_model):
         return H <= 16 and d_model in (512, 768, 1024)
 
-    def xattn_decode(self, Q, E, k_off, part_ml, part_c):
-        """one decode step, scores + softmax + context of a key range per workgroup: Q [B, R <= 16, D] bf16 view,
-        part_ml [Z, B, 16, 2] / part_c [Z, B, 16, D] fp32 (contiguous) receive every range's (max, Σ exp) and Σ exp·E"""
+    @staticmethod
+    def _xattn_decode_args(Q, E, k_off, part_ml, part_c):
+        """the arguments of lako_xattn_decode / lako_xattn_decode_plan up to the stream / the plan"""
         Bz, R, D = Q.shape
         Z = part_c.shape[0]
         if part_c.shape != (Z, Bz, 16, D) or part_ml.shape != (Z, Bz, 16, 2) or not part_c.is_contiguous() or not part_ml.is_contiguous() \
                 or Q.stride(2) != 1 or E.stride(1) != 1 or E.shape[1] != D:
             raise LakoError(f"xattn_decode: shapes Q{tuple(Q.shape)} E{tuple(E.shape)} part{tuple(part_c.shape)}")
-        self._timed("xattn", 4.0 * R * D * E.shape[0], lambda: check(self.lib.lako_xattn_decode(
-            _p(Q), Q.stride(0), Q.stride(1), _p(E), E.stride(0), _p(k_off), _p(part_ml), _p(part_c), R, D, Bz, Z, self._stream()),
-            "lako_xattn_decode"))
+        return (_p(Q), Q.stride(0), Q.stride(1), _p(E), E.stride(0), _p(k_off), _p(part_ml), _p(part_c), R, D, Bz, Z)
+
+    def xattn_decode(self, Q, E, k_off, part_ml, part_c):
+        """one decode step, scores + softmax + context of a key range per workgroup: Q [B, R <= 16, D] bf16 view,
+        part_ml [Z, B, 16, 2] / part_c [Z, B, 16, D] fp32 (contiguous) receive every range's (max, Σ exp) and Σ exp·E"""
+        args = self._xattn_decode_args(Q, E, k_off, part_ml, part_c)
+        self._timed("xattn", 4.0 * args[8] * args[9] * E.shape[0], lambda: check(self.lib.lako_xattn_decode(*args, self._stream()),
+                                                                               "lako_xattn_decode"))
+
+    def xattn_decode_plan(self, Q, E, k_off, part_ml, part_c):
+        """the launch xattn_decode would make for these arguments (lako_xattn_decode_plan: nothing launched)"""
+        from ._lib import XattnPlan
+        plan = XattnPlan()
+        check(self.lib.lako_xattn_decode_plan(*self._xattn_decode_args(Q, E, k_off, part_ml, part_c), C.byref(plan)), "lako_xattn_decode_plan")
+        return plan
 
     def xattn_decode_combine(self, part_ml, part_c, Wv, ctx, H):
         """ctx [B, H·64] bf16 = (merged ranges of xattn_decode)·Wvᵀ per head; Wv [H·64, D] bf16 rows of the V projection"""
@@ -676,6 +701,18 @@ class HipOps:
         self._timed("xattn_softmax", 0.0, lambda: check(self.lib.lako_xattn_softmax_bwd(
             _p(S), _p(dP), S.stride(0), _p(stats), _p(dS), dS.stride(0), _p(k_off), _p(p_off), Bz, T, H, int(max_keys),
             _drop(drop), self._stream()), "lako_xattn_softmax_bwd"))
+
+    def xattn_softmax_plan(self, S, stats, P, k_off, p_off, T, H, max_keys, drop=None, dP=None):
+        """the launch xattn_softmax_fwd (dP None) / xattn_softmax_bwd (dP given, P = dS) would make (lako_xattn_softmax_plan: the same
+        arguments, nothing launched)"""
+        from ._lib import XattnPlan
+        if dP is not None and dP.stride(0) != S.stride(0):
+            raise LakoError("xattn_softmax_bwd: S and dP must share their row stride")
+        plan = XattnPlan()
+        check(self.lib.lako_xattn_softmax_plan(int(dP is not None), _p(S), _p(dP), S.stride(0), _p(stats), _p(P), P.stride(0), _p(k_off),
+                                               _p(p_off), stats.shape[0], T, H, int(max_keys), _drop(drop), C.byref(plan)),
+              "lako_xattn_softmax_plan")
+        return plan
 
     # ---- loss / optimizer ---------------------------------------------------------------------------
     def ce_fwd_bwd(self, logits, labels, loss_out, dlogits, upstream=None):

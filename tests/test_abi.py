@@ -56,7 +56,7 @@ def test_struct_layouts_match_header_order():
     for cname, py in (("lako_gemm_nt_t", _lib.GemmNT), ("lako_attn_fwd_t", _lib.AttnFwd), ("lako_attn_bwd_t", _lib.AttnBwd),
                       ("lako_dropout_t", _lib.Dropout), ("lako_headbatch_t", _lib.HeadBatch),
                       ("lako_gemm_tn_item_t", _lib.GemmTNItem), ("lako_gemm_plan_t", _lib.GemmPlan), ("lako_gemm_tn_plan_t", _lib.GemmTNPlan),
-                      ("lako_attn_launch_t", _lib.AttnLaunch)):
+                      ("lako_attn_launch_t", _lib.AttnLaunch), ("lako_xattn_plan_t", _lib.XattnPlan)):
         body = re.search(r"typedef struct \{([^{}]*)\}\s*" + cname, src, re.S).group(1)
         names = []
         for decl in body.split(";"):
@@ -138,6 +138,23 @@ def test_bad_arguments_return_error_codes(lib):
     a.q_stride_t = a.k_stride_t = a.v_stride_t = a.o_stride_t = 32
     assert L.lako_attn_fwd_plan(ctypes.byref(a), ctypes.byref(ap)) == 0 and ap.n_launches == 1 and ap.launch[0].kernel == _lib.ATTN_FWD
     assert ctypes.sizeof(_lib.AttnPlan) == 4 + 2 * 20 * 4
+    # ... and the cross-attention's three: null outputs, the refusals of the launching calls (above: R > 16 rows, s_ld % 4, an all-zero
+    # lako_headbatch_t) with a zeroed plan, a valid query each
+    xp = _lib.XattnPlan()
+    assert L.lako_xattn_decode_plan(x, 8, 8, x, 768, x, x, x, 12, 768, 16, 16, None) == -1
+    assert L.lako_xattn_decode_plan(x, 8, 8, x, 768, x, x, x, 12, 768, 16, 16, ctypes.byref(xp)) == 0 and xp.kernel == _lib.XK_DECODE
+    assert L.lako_xattn_decode_plan(x, 8, 8, x, 768, x, x, x, 17, 768, 16, 16, ctypes.byref(xp)) == -1 and xp.kernel == 0 and xp.block == 0
+    assert L.lako_xattn_softmax_plan(0, x, None, 256, x, x, 256, x, x, 16, 8, 12, 4000, _lib.NO_DROP, None) == -1
+    assert L.lako_xattn_softmax_plan(0, x, None, 256, x, x, 256, x, x, 16, 8, 12, 4000, _lib.NO_DROP, ctypes.byref(xp)) == 0
+    assert (xp.kernel, xp.nv, xp.bwd) == (_lib.XK_SOFTMAX_REG, 4, 0)
+    assert L.lako_xattn_softmax_plan(0, x, None, 255, x, x, 256, x, x, 16, 8, 12, 4000, _lib.NO_DROP, ctypes.byref(xp)) == -1 and xp.kernel == 0
+    assert L.lako_xattn_softmax_plan(1, x, None, 256, x, x, 256, x, x, 16, 8, 12, 4000, _lib.NO_DROP, ctypes.byref(xp)) == -1      # bwd: null dp
+    assert L.lako_xattn_softmax_bwd(x, None, 256, x, x, 256, x, x, 16, 8, 12, 4000, _lib.NO_DROP, None) == -1
+    assert L.lako_headbatch_nt_plan(ctypes.byref(hb), None) == -1 and L.lako_headbatch_nt_plan(None, ctypes.byref(xp)) == -1
+    assert L.lako_headbatch_nt_plan(ctypes.byref(hb), ctypes.byref(xp)) == -1 and xp.kernel == 0
+    hb.a, hb.b, hb.c, hb.M, hb.T, hb.H, hb.N, hb.K, hb.a_dtype, hb.b_dtype, hb.ldb = 4096, 8192, 12288, 16, 8, 12, 64, 768, 1, 1, 768
+    assert L.lako_headbatch_nt_plan(ctypes.byref(hb), ctypes.byref(xp)) == 0 and (xp.kernel, xp.ks) == (_lib.XK_HB_CONTRACT, 6)
+    assert ctypes.sizeof(_lib.XattnPlan) == 13 * 4
 
 
 def test_comm_and_workspace_entry_points_validate_their_arguments(lib):
