@@ -490,7 +490,8 @@ enum {
   LAKO_XK_SOFTMAX = 2,     /* xsoftmax_kernel<bwd>: any length, the row is read once per pass */
   LAKO_XK_HB_CONTRACT = 3, /* hb_contract_kernel<af32, ks>: N = 64, K = 128 * ks in {512, 768, 1024} */
   LAKO_XK_HB_NT = 4,       /* hb_nt_kernel<af32, nt, ku>: every other head-batched NT product */
-  LAKO_XK_DECODE = 5       /* xdecode_kernel<ks>: D = 256 * ks, a ring of `stages` LDS stages */
+  LAKO_XK_DECODE = 5,      /* xdecode_kernel<ks>: D = 256 * ks, a ring of `stages` LDS stages */
+  LAKO_XK_DECODE_MULTI = 6 /* xdecode_kernel<ks, nt>: the same with nt row tiles (sequences of one sample) per workgroup */
 };
 typedef struct {
   int32_t kernel; /* LAKO_XK_* */
@@ -498,10 +499,10 @@ typedef struct {
   int32_t bwd;    /* softmax: the backward instantiation */
   int32_t nv;     /* LAKO_XK_SOFTMAX_REG: 16-byte vectors per thread, 4 | 8 */
   int32_t af32;   /* head-batched products: A is fp32 (key-split slabs summed on the way in) */
-  int32_t nt;     /* LAKO_XK_HB_NT: 16-column tiles per wave, 4 | 1 */
+  int32_t nt;     /* LAKO_XK_HB_NT: 16-column tiles per wave, 4 | 1; LAKO_XK_DECODE_MULTI: row tiles per workgroup, 4 | 2 | 1 */
   int32_t ku;     /* LAKO_XK_HB_NT: K-steps of 32 loaded together, 8 | 2 | 1 */
-  int32_t ks;     /* LAKO_XK_HB_CONTRACT: K-steps of 32 per wave (K / 128); LAKO_XK_DECODE: K-steps per wave (D / 256) */
-  int32_t stages; /* LAKO_XK_DECODE: stages of the LDS ring, 3 | 2 */
+  int32_t ks;     /* LAKO_XK_HB_CONTRACT: K-steps of 32 per wave (K / 128); LAKO_XK_DECODE(_MULTI): K-steps per wave (D / 256) */
+  int32_t stages; /* LAKO_XK_DECODE(_MULTI): stages of the LDS ring, 3 | 2 */
   /* the launch */
   int32_t gx, gy, gz; /* grid, in workgroups */
   int32_t block;      /* threads per workgroup */
@@ -513,6 +514,21 @@ int lako_xattn_softmax_plan(int bwd, const float* s, const float* dp, int64_t s_
 int lako_headbatch_nt_plan(const lako_headbatch_t* p, lako_xattn_plan_t* out);
 int lako_xattn_decode_plan(const void* q, int64_t q_sb, int64_t q_ld, const void* e, int64_t e_ld, const int32_t* k_off,
                            float* part_ml, float* part_c, int R, int D, int B, int key_splits, lako_xattn_plan_t* out);
+
+/* lako_xattn_decode for K sequences per sample that attend to the SAME keys (sampled decoding: K answers per question over one copy
+ * of the encoder states): q bf16 [B][K][R <= 16][D] (sample stride q_sb, sequence stride q_sk, row stride q_ld, in elements),
+ * part_ml [Z][B*K][16][2], part_c [Z][B*K][16][D]: for every sequence the very bits lako_xattn_decode writes for that sequence's
+ * queries alone, so lako_xattn_decode_combine finishes with B := B*K.  A workgroup carries `nt` sequences (row tiles) through one
+ * pass over its key range: the encoder states are read once per nt sequences instead of once per sequence.  rt = 0: the library's
+ * rule picks nt (the largest of 4 | 2 | 1 that is <= K and that the kernel is built for at this D); rt = 1 | 2 | 4 forces it
+ * (refused where the kernel is not built: rt = 4 at D = 1024).  Refusals are lako_xattn_decode's, plus K < 1.  The plan query
+ * reports kernel LAKO_XK_DECODE_MULTI, ks, nt, stages, lds and the grid (key_splits, B, ceil(K / nt)); it makes no HIP call. */
+int lako_xattn_decode_multi(const void* q, int64_t q_sb, int64_t q_sk, int64_t q_ld, const void* e, int64_t e_ld,
+                            const int32_t* k_off, float* part_ml, float* part_c, int R, int D, int B, int K, int key_splits, int rt,
+                            lako_stream_t stream);
+int lako_xattn_decode_multi_plan(const void* q, int64_t q_sb, int64_t q_sk, int64_t q_ld, const void* e, int64_t e_ld,
+                                 const int32_t* k_off, float* part_ml, float* part_c, int R, int D, int B, int K, int key_splits,
+                                 int rt, lako_xattn_plan_t* out);
 
 /* ---- LM-head loss (HF5:1051-1054): CrossEntropyLoss(ignore_index=-100), mean over valid labels ----
  * logits fp32 [M, V]; loss_out[0] = mean loss, loss_out[1] = number of valid labels;
@@ -571,6 +587,25 @@ int lako_pack_ids(const int64_t* ids, const int32_t* off, int64_t* out, int BN, 
  * n_done[0] = number of finished rows after the step. */
 int lako_greedy_step(const float* logits, int64_t V, int B, int64_t* seq, int64_t seq_ld, int pos, int64_t* next_ids,
                      uint8_t* done, int32_t* n_done, int64_t eos_id, int64_t pad_id, lako_stream_t stream);
+/* sampled step (HF generate, do_sample=True: temperature, top-k, top-p, multinomial draw) for `rows` rows of fp32 logits [rows, V];
+ * row r is sequence r % group of question r / group.  params: DEVICE memory, 8 32-bit words read by the kernel (so that a captured
+ * launch follows a caller's changes): [0] temperature (float > 0), [1] top_p (float in (0, 1]), [2] top_k (int32, 0 = off),
+ * [3], [4] low / high word of the seed, [5..7] reserved.  Per row that is not done:
+ *   w_i = floor(2^40 * exp((x_i - max x) / temperature)) (x = logits[r], NaN counts as -inf; exp in fp32, sums in exact integers);
+ *   top-k: if 0 < top_k < V keep the top_k largest x, equal values by ascending index;
+ *   top-p: if top_p < 1, in the order (x descending, index ascending) keep the shortest prefix of the kept whose mass reaches
+ *          ceil(top_p * their mass), at least one token;
+ *   draw:  a = hash32(seed_lo + 0x9E3779B9 * (r % group)), h = hash32((a ^ seed_hi) + 0x85EBCA6B * step + 0x1234567), U = h >> 8,
+ *          hash32 = the lowbias32 finalizer (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16), all mod 2^32;
+ *          token = the first kept index, ascending, whose running kept mass exceeds floor(U * (kept mass) / 2^24);
+ *   seq[r*seq_ld + pos] = next_ids[r] = token; done[r] |= token == eos_id; score[r] += log_softmax(x)[token] (score may be NULL) —
+ *   the model's own log-probability of the token: neither the temperature nor the truncation enters it.
+ * A done row emits pad_id and leaves its score alone; a row without a finite logit emits id 0; a logit of -inf is never drawn.
+ * n_done[0] = number of finished rows after the step.  The same inputs give the same tokens on every launch (no float atomics).
+ * top_k = 1 is the greedy step (lowest index among equal maxima) with the score added. */
+int lako_sample_step(const float* logits, int64_t V, int rows, int group, int64_t* seq, int64_t seq_ld, int pos, int64_t* next_ids,
+                     uint8_t* done, float* score, int32_t* n_done, const void* params, int step, int64_t eos_id, int64_t pad_id,
+                     lako_stream_t stream);
 
 /* ---- per-fact aggregation of the captured step-0 cross-attention scores (src/model.py:100-115,143-204,
  * FiDT5.get_crossattention_scores; replaces its per-sample Python loops) ----------------------------------------------------

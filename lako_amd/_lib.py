@@ -141,7 +141,7 @@ class XattnPlan(C.Structure):
 
 
 # lako_xattn_plan_t.kernel (include/lako_hip.h LAKO_XK_*)
-XK_NONE, XK_SOFTMAX_REG, XK_SOFTMAX, XK_HB_CONTRACT, XK_HB_NT, XK_DECODE = range(6)
+XK_NONE, XK_SOFTMAX_REG, XK_SOFTMAX, XK_HB_CONTRACT, XK_HB_NT, XK_DECODE, XK_DECODE_MULTI = range(7)
 
 
 # name -> argtypes (restype is always int).  Must list EVERY function include/lako_hip.h declares:
@@ -188,6 +188,8 @@ SIGNATURES = {
     "lako_xattn_decode": [vp, i64, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp],
     "lako_xattn_decode_plan": [vp, i64, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, C.POINTER(XattnPlan)],
     "lako_xattn_decode_combine": [vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "lako_xattn_decode_multi": [vp, i64, i64, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "lako_xattn_decode_multi_plan": [vp, i64, i64, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(XattnPlan)],
     "lako_xattn_softmax_plan": [i32, vp, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, i32, Dropout, C.POINTER(XattnPlan)],
     "lako_headbatch_nt": [C.POINTER(HeadBatch), vp],
     "lako_headbatch_nt_plan": [C.POINTER(HeadBatch), C.POINTER(XattnPlan)],
@@ -206,6 +208,7 @@ SIGNATURES = {
     "lako_shift_right": [vp, vp, i32, i32, vp],
     "lako_pack_ids": [vp, vp, vp, i32, i32, vp],
     "lako_greedy_step": [vp, i64, i32, vp, i64, i32, vp, vp, vp, i64, i64, vp],
+    "lako_sample_step": [vp, i64, i32, i32, vp, i64, i32, vp, vp, vp, vp, vp, i32, i64, i64, vp],
     "lako_fact_scores": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "lako_topk": [vp, i64, i64, i64, i32, vp, vp, vp],
     "lako_pq_assign": [vp, i64, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp],

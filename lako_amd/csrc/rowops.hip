@@ -1172,6 +1172,261 @@ __global__ void count_done_kernel(const uint8_t* done, int B, int32_t* n_done) {
   if (threadIdx.x == 0) n_done[0] = cnt;
 }
 
+// ---- sampled decoding step (HF generate, do_sample=True: temperature → top-k → top-p → multinomial) --------------------------
+// One workgroup of 1024 threads per row r.  params (device, 8 words): [0] temperature f32, [1] top_p f32, [2] top_k i32,
+// [3] seed low word, [4] seed high word.  With x = logits[r] (a NaN counts as −∞) and m = max x:
+//   weight   w_i = ⌊2^40·exp((x_i − m) / temperature)⌋, an INTEGER (exp in fp32).  Every mass below is a sum of these integers: exact,
+//            whatever order the atomics and reductions add them in — the same input gives the same token on every launch.
+//   top-k    (0 < top_k < V) keep the top_k largest x, equal values by ascending index.
+//   top-p    (top_p < 1) among those, in the order (x descending, index ascending), keep the shortest prefix whose mass reaches
+//            ⌈top_p·(mass of the kept)⌉; at least one token.
+//   draw     a = lako_hash32(seed_lo + 0x9E3779B9·(r mod K)),  h = lako_hash32((a ^ seed_hi) + 0x85EBCA6B·step + 0x1234567),  U = h >> 8
+//            (u = U·2^−24 ∈ [0, 1)); the token is the first kept index, ascending, whose running kept mass exceeds ⌊U·(kept mass) / 2^24⌋.
+//            r mod K: K = sequences per question, so that sequence k of a question draws the same u wherever the question sits in a batch.
+//   score[r] += x_token − (m + log Σ exp(x − m)): the model's own log-probability, in fp32 with a fixed summation order.
+// Thresholds come from a radix select over the order-preserving integer image of x, four passes of 8 bits: a COUNT histogram for
+// top-k, a MASS histogram for top-p (LDS atomics on 64-bit integers; a thread merges runs of equal digits before it adds).  Every
+// pass walks the row in LDS (V·4 bytes next to 2.3 KB of histograms; LDSROW = false: the row does not fit and is re-read from L2),
+// thread t owning the contiguous indices [t·CH, (t+1)·CH), CH odd (conflict-free strides), so that index order is thread order.
+// A row without any finite logit (all NaN / −∞) emits id 0; a done row emits pad and leaves its score alone.
+struct SampleArgs {
+  const float* logits;
+  int64_t V;
+  int64_t* seq;
+  int64_t seq_ld;
+  int64_t* next_ids;
+  uint8_t* done;
+  float* score;
+  const uint32_t* params;
+  int64_t eos, pad;
+  int pos, K;
+  uint32_t step;
+};
+constexpr int SMP_T = 1024;
+
+__device__ __forceinline__ uint32_t smp_key(float x) {      // x > y ⟺ key(x) > key(y) for non-NaN x, y (−0 is canonicalised by the reader)
+  const uint32_t b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long smp_weight(float x, float m, float temp) {
+  return (unsigned long long)(__expf((x - m) / temp) * 1099511627776.f);
+}
+// exclusive prefix of v over the workgroup's threads in thread order, and the total
+__device__ __forceinline__ unsigned long long smp_scan(unsigned long long v, unsigned long long* wsum, unsigned long long& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long n = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += n;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  unsigned long long base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < SMP_T / 64; ++w) {
+    const unsigned long long s = wsum[w];
+    if (w < wave) base += s;
+    tot += s;
+  }
+  __syncthreads();
+  total = tot;
+  return base + inc - v;
+}
+
+template <bool LDSROW>
+__global__ __launch_bounds__(SMP_T) void sample_step_kernel(SampleArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smp_smem[];
+  __shared__ unsigned long long hist[256];
+  __shared__ unsigned long long wsum[SMP_T / 64];
+  __shared__ unsigned long long sel[2];
+  __shared__ float fred[2][SMP_T / 64];
+  __shared__ int64_t pick;
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (a.done[r]) {       // the same for every thread of the workgroup
+    if (tid == 0) {
+      a.seq[(int64_t)r * a.seq_ld + a.pos] = a.pad;
+      a.next_ids[r] = a.pad;
+    }
+    return;
+  }
+  const int V = (int)a.V;
+  const float* g = a.logits + (int64_t)r * a.V;
+  float* row = reinterpret_cast<float*>(smp_smem);
+  const float temp = __uint_as_float(a.params[0]), top_p = __uint_as_float(a.params[1]);
+  const int top_k = (int)a.params[2];
+  const uint32_t seed_lo = a.params[3], seed_hi = a.params[4];
+  auto canon = [](float x) { return x != x ? -INFINITY : (x == 0.f ? 0.f : x); };
+  auto get = [&](int i) { return LDSROW ? row[i] : canon(g[i]); };
+  const int CH = ((V + SMP_T - 1) / SMP_T) | 1;
+  const int i0 = min((int64_t)V, (int64_t)tid * CH), i1 = min((int64_t)V, (int64_t)tid * CH + CH);
+
+  // ---- the row (once from HBM), its maximum and Σ exp(x − m) of the raw logits -------------------------------------------------
+  float m = -INFINITY;
+  for (int i = tid; i < V; i += SMP_T) {
+    const float x = canon(g[i]);
+    if (LDSROW) row[i] = x;
+    m = fmaxf(m, x);
+  }
+  m = wave_max(m);
+  if (lane == 0) fred[0][wave] = m;
+  __syncthreads();
+  m = fred[0][0];
+#pragma unroll
+  for (int w = 1; w < SMP_T / 64; ++w) m = fmaxf(m, fred[0][w]);
+  if (!(m > -INFINITY)) {      // no finite logit (uniform): id 0, as the greedy step
+    if (tid == 0) {
+      a.seq[(int64_t)r * a.seq_ld + a.pos] = 0;
+      a.next_ids[r] = 0;
+      if (a.eos == 0) a.done[r] = 1;
+    }
+    return;
+  }
+  float se = 0.f;
+  for (int i = i0; i < i1; ++i) se += __expf(get(i) - m);
+  se = wave_sum(se);
+  if (lane == 0) fred[1][wave] = se;      // read after the barriers below
+
+  // kept(key, i) ⟺ key > thr || (key == thr && i <= cut): everything to begin with
+  uint32_t thr = 0;
+  int cut = V;
+  // one radix select: the key at which the running count / mass, from the largest key down, reaches `need`, and what of `need` is left for that key
+  auto select = [&](unsigned long long need, bool mass, uint32_t kthr, int kcut, uint32_t& key_out, unsigned long long& rem_out) {
+    uint32_t prefix = 0, pmask = 0;
+    for (int sh = 24; sh >= 0; sh -= 8) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      int cur = -1;
+      unsigned long long acc = 0;
+      for (int i = i0; i < i1; ++i) {
+        const float x = get(i);
+        const uint32_t key = smp_key(x);
+        if ((key & pmask) != prefix || !(key > kthr || (key == kthr && i <= kcut))) continue;
+        const unsigned long long w = mass ? smp_weight(x, m, temp) : 1ull;
+        const int d = (int)((key >> sh) & 255u);
+        if (d != cur) {
+          if (acc) atomicAdd(&hist[cur], acc);
+          cur = d;
+          acc = 0;
+        }
+        acc += w;
+      }
+      if (acc) atomicAdd(&hist[cur], acc);
+      __syncthreads();
+      if (wave == 0) {
+        const unsigned long long h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+        const unsigned long long s = h0 + h1 + h2 + h3;
+        unsigned long long inc = s;      // Σ over the lanes >= this one: the bins from the largest digit down
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const unsigned long long n = __shfl_down(inc, o, 64);
+          if (lane + o < 64) inc += n;
+        }
+        const unsigned long long above = inc - s;
+        if (lane == 0 && need > inc) {      // cannot happen (need <= the total by construction): keep the walk defined
+          sel[0] = 0;
+          sel[1] = 1;
+        }
+        if (above < need && need <= inc) {
+          unsigned long long rem = need - above;
+          int d;
+          if (rem <= h3) d = 3;
+          else {
+            rem -= h3;
+            if (rem <= h2) d = 2;
+            else {
+              rem -= h2;
+              if (rem <= h1) d = 1;
+              else { rem -= h1; d = 0; }
+            }
+          }
+          sel[0] = (unsigned long long)(4 * lane + d);
+          sel[1] = rem;
+        }
+      }
+      __syncthreads();
+      prefix |= (uint32_t)sel[0] << sh;
+      pmask |= 255u << sh;
+      need = sel[1];
+    }
+    key_out = prefix;
+    rem_out = need;
+  };
+  // the index of the n-th (n >= 1) element, ascending, with this key among the kept ones
+  auto nth_equal = [&](uint32_t key_eq, unsigned long long n, uint32_t kthr, int kcut) {
+    unsigned long long c = 0, tot;
+    for (int i = i0; i < i1; ++i) c += (smp_key(get(i)) == key_eq && (key_eq > kthr || i <= kcut)) ? 1ull : 0ull;
+    const unsigned long long ex = smp_scan(c, wsum, tot);
+    if (tid == 0) pick = V;              // n > the number of equal elements: all of them
+    __syncthreads();
+    if (ex < n && n <= ex + c) {
+      unsigned long long left = n - ex;
+      for (int i = i0; i < i1; ++i)
+        if (smp_key(get(i)) == key_eq && (key_eq > kthr || i <= kcut) && --left == 0) { pick = i; break; }
+    }
+    __syncthreads();
+    const int res = (int)pick;
+    __syncthreads();
+    return res;
+  };
+
+  if (top_k > 0 && top_k < V) {
+    unsigned long long ties;
+    uint32_t kk;
+    select((unsigned long long)top_k, false, 0u, V, kk, ties);
+    cut = nth_equal(kk, ties, 0u, V);
+    thr = kk;
+  }
+  if (top_p < 1.f) {
+    unsigned long long c = 0, tot, rem;
+    for (int i = i0; i < i1; ++i) {
+      const float x = get(i);
+      const uint32_t key = smp_key(x);
+      if (key > thr || (key == thr && i <= cut)) c += smp_weight(x, m, temp);
+    }
+    smp_scan(c, wsum, tot);
+    unsigned long long need = (unsigned long long)ceil((double)top_p * (double)tot);
+    need = need < 1 ? 1 : (need > tot ? tot : need);
+    uint32_t kp;
+    select(need, true, thr, cut, kp, rem);
+    const unsigned long long w = smp_weight(__uint_as_float((kp & 0x80000000u) ? (kp & 0x7FFFFFFFu) : ~kp), m, temp);   // > 0: its bin held mass
+    const int c2 = nth_equal(kp, (rem + w - 1) / (w ? w : 1), thr, cut);
+    thr = kp;
+    cut = c2;
+  }
+
+  // ---- the draw, in index order ---------------------------------------------------------------------------------------------
+  unsigned long long c = 0, tot;
+  for (int i = i0; i < i1; ++i) {
+    const float x = get(i);
+    const uint32_t key = smp_key(x);
+    if (key > thr || (key == thr && i <= cut)) c += smp_weight(x, m, temp);
+  }
+  const unsigned long long ex = smp_scan(c, wsum, tot);
+  const uint32_t ha = lako_hash32(seed_lo + 0x9E3779B9U * (uint32_t)(r % a.K));
+  const uint32_t U = lako_hash32((ha ^ seed_hi) + 0x85EBCA6BU * a.step + 0x1234567U) >> 8;
+  const unsigned long long target = (__umul64hi((unsigned long long)U, tot) << 40) | (((unsigned long long)U * tot) >> 24);   // < tot
+  if (ex <= target && target < ex + c) {      // exactly one thread (tot >= the maximum's 2^40 > 0)
+    unsigned long long run = ex;
+    for (int i = i0; i < i1; ++i) {
+      const float x = get(i);
+      const uint32_t key = smp_key(x);
+      if (!(key > thr || (key == thr && i <= cut))) continue;
+      run += smp_weight(x, m, temp);
+      if (run > target) {
+        float s = fred[1][0];
+#pragma unroll
+        for (int w = 1; w < SMP_T / 64; ++w) s += fred[1][w];
+        a.seq[(int64_t)r * a.seq_ld + a.pos] = i;
+        a.next_ids[r] = i;
+        if (i == a.eos) a.done[r] = 1;
+        if (a.score) a.score[r] += (x - m) - __logf(s);
+        break;
+      }
+    }
+  }
+}
+
 // ---- per-fact aggregation of captured cross-attention scores (src/model.py:100-115,143-204) ----------------
 // One workgroup per sample.  vals[l] = Σ_{head, layer} scores[b, h, layer, p0·L + l] over the layers [ly0, ly0 + nly), masked
 // positions 0 (the reference's masked_fill + sum(dim=[1,2]), rounded to fp32 like its tensor).  The token ids that define the spans
@@ -1608,6 +1863,29 @@ extern "C" int lako_greedy_step(const float* logits, int64_t V, int B, int64_t* 
   hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, V, seq, seq_ld, pos,
                      next_ids, done, eos_id, pad_id);
   hipLaunchKernelGGL(count_done_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, done, B, n_done);
+  LAKO_LAUNCH_CHECK();
+  return LAKO_OK;
+}
+
+extern "C" int lako_sample_step(const float* logits, int64_t V, int rows, int group, int64_t* seq, int64_t seq_ld, int pos,
+                                int64_t* next_ids, uint8_t* done, float* score, int32_t* n_done, const void* params, int step,
+                                int64_t eos_id, int64_t pad_id, lako_stream_t stream) {
+  LAKO_CHECK_ARG(logits && seq && next_ids && done && n_done && params, "lako_sample_step: null operand");
+  LAKO_CHECK_ARG(rows > 0 && group > 0 && V > 0 && V < (1ll << 30) && pos >= 0 && pos < seq_ld && step >= 0,
+                 "lako_sample_step: bad dims (rows=%d group=%d V=%lld pos=%d step=%d)", rows, group, (long long)V, pos, step);
+  LAKO_CHECK_ALIGN(params, 4);
+  SampleArgs a{};
+  a.logits = logits; a.V = V; a.seq = seq; a.seq_ld = seq_ld; a.next_ids = next_ids; a.done = done; a.score = score;
+  a.params = (const uint32_t*)params; a.eos = eos_id; a.pad = pad_id; a.pos = pos; a.K = group; a.step = (uint32_t)step;
+  const size_t row_b = ((size_t)V * 4 + 15) & ~(size_t)15;
+  if (row_b + 4096 <= 160 * 1024) {      // the row next to the static histograms / scan slots
+    static lako_lds_cur_t cur;
+    lako_raise_max_lds(reinterpret_cast<const void*>(&sample_step_kernel<true>), (int)row_b, cur);
+    hipLaunchKernelGGL((sample_step_kernel<true>), dim3(rows), dim3(SMP_T), row_b, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL((sample_step_kernel<false>), dim3(rows), dim3(SMP_T), 0, (hipStream_t)stream, a);
+  }
+  hipLaunchKernelGGL(count_done_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, done, rows, n_done);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
 }

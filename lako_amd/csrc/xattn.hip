@@ -277,16 +277,23 @@ struct XdArgs {
   float* part_ml;       // [Z][B][16][2]
   float* part_c;        // [Z][B][16][D]
   int R, D, B, Z;
+  int K;                // lako_xattn_decode_multi: sequences per sample (q [B][K][R][D], sequence stride q_sk; partials [Z][B·K][16][…]); else 1
+  int64_t q_sk;
 };
 
-template <int KS>      // K-steps (of 32 dims) per wave: D = 256·KS
+// RT row tiles per workgroup (lako_xattn_decode_multi): the K sequences of a sample attend to the SAME keys, so a stage of 32 keys is
+// loaded once and feeds RT score tiles and RT context accumulations — each tile with its own queries, online-softmax state, context
+// accumulators and 16 KiB of partial-score exchange; tile rt of workgroup (z, b, zt) is sequence zt·RT + rt (a tile past K computes on
+// zero queries and stores nothing).  Per row the operations and their order are those of RT = 1: the partials are the same bits.
+template <int KS, int RT = 1>      // K-steps (of 32 dims) per wave: D = 256·KS
 __global__ __launch_bounds__(512, 1) void xdecode_kernel(XdArgs a) {
-  extern __shared__ __attribute__((aligned(1024))) char smem[];   // 2 stages [32][D] | partial score tiles [8][32][16] fp32
+  extern __shared__ __attribute__((aligned(1024))) char smem[];   // NSTG stages [32][D] | RT × partial score tiles [8][32][16] fp32
   constexpr int D = 256 * KS, STAGE = 32 * D * 2, NIMG = D / 64, NDB = D / 128;   // NDB: 16-column blocks per wave
-  constexpr int NSTG = 3 * STAGE + 8 * 32 * 16 * 4 <= 160 * 1024 ? 3 : 2;        // stages of the ring (one or two in flight)
+  constexpr int RED = 8 * 32 * 16;                                                  // floats of one tile's score exchange
+  constexpr int NSTG = 3 * STAGE + RT * RED * 4 <= 160 * 1024 ? 3 : 2;             // stages of the ring (one or two in flight)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, l15 = lane & 15;
-  const int z = blockIdx.x, b = blockIdx.y;
+  const int z = blockIdx.x, b = blockIdx.y, seq0 = blockIdx.z * RT;
   const int kfirst = __builtin_amdgcn_readfirstlane(a.k_off[b]);
   const int Sb = __builtin_amdgcn_readfirstlane(a.k_off[b + 1]) - kfirst;
   const int nst_all = (Sb + 31) >> 5;
@@ -297,16 +304,22 @@ __global__ __launch_bounds__(512, 1) void xdecode_kernel(XdArgs a) {
   float* sred = reinterpret_cast<float*>(smem + NSTG * STAGE);
 
   // the wave's slice of the expanded queries: row l15, dims (wave·KS + t)·32 + 8g … as MFMA fragments
-  u32x4 qf[KS];
+  u32x4 qf[RT][KS];
 #pragma unroll
-  for (int t = 0; t < KS; ++t) {
-    qf[t] = u32x4{0u, 0u, 0u, 0u};
-    if (l15 < a.R) qf[t] = *reinterpret_cast<const u32x4*>(a.q + ((int64_t)b * a.q_sb + (int64_t)l15 * a.q_ld + (wave * KS + t) * 32 + 8 * g) * 2);
-  }
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+      qf[rt][t] = u32x4{0u, 0u, 0u, 0u};
+      if (l15 < a.R && seq0 + rt < a.K)
+        qf[rt][t] = *reinterpret_cast<const u32x4*>(a.q + ((int64_t)b * a.q_sb + (int64_t)(seq0 + rt) * a.q_sk + (int64_t)l15 * a.q_ld +
+                                                            (wave * KS + t) * 32 + 8 * g) * 2);
+    }
   // a USE of the loaded registers that the compiler sees: it waits for these loads HERE, not at their first use inside the loop
   // (an s_waitcnt vmcnt(0) there would also wait for every LDS-DMA stage in flight)
 #pragma unroll
-  for (int t = 0; t < KS; ++t) asm volatile("" : "+v"(qf[t]));
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int t = 0; t < KS; ++t) asm volatile("" : "+v"(qf[rt][t]));
 
   auto issue = [&](int i) {      // stage i of this workgroup: keys (st_begin + i)·32 …, NIMG images of 4 instructions
     char* stage = smem + (i % NSTG) * STAGE;
@@ -319,7 +332,7 @@ __global__ __launch_bounds__(512, 1) void xdecode_kernel(XdArgs a) {
     }
   };
 
-  f32x4 cacc[NDB];
+  f32x4 cacc[RT][NDB];
   // byte offset of the wave's column block db inside a stage (image + transposed-read offset), computed — NOT el.toff[runtime index]:
   // at D = 768 the block index depends on the wave, a dynamically indexed register array lands in scratch memory, and every
   // scratch reload is a vector-memory operation whose s_waitcnt vmcnt(0) also waits for the LDS-DMA stages in flight (the ring
@@ -327,7 +340,8 @@ __global__ __launch_bounds__(512, 1) void xdecode_kernel(XdArgs a) {
   uint32_t coff[NDB];
 #pragma unroll
   for (int db = 0; db < NDB; ++db) {
-    cacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) cacc[rt][db] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int col = wave * (D / 8) + db * 16, tr = 4 * g + (l15 >> 2);
     coff[db] = (uint32_t)((col >> 6) * 32 * EROW + tr * EROW + ((((col & 63) >> 4) ^ ((tr >> 1) & 3)) << 5) + (l15 & 3) * 8);
   }
@@ -337,7 +351,9 @@ __global__ __launch_bounds__(512, 1) void xdecode_kernel(XdArgs a) {
     const int sidx = wave * KS + t;
     soff[t] = (uint32_t)((sidx >> 1) * 32 * EROW + l15 * EROW + eswz((sidx & 1) * 4 + g, l15) * 16);
   }
-  float m_run = -INFINITY, l_run = 0.f;
+  float m_run[RT], l_run[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) m_run[rt] = -INFINITY, l_run[rt] = 0.f;
 
   if (nst > 0) issue(0);
   if (NSTG == 3 && nst > 1) issue(1);
@@ -348,68 +364,80 @@ __global__ __launch_bounds__(512, 1) void xdecode_kernel(XdArgs a) {
     if (i + NSTG - 1 < nst) issue(i + NSTG - 1);
     const char* stage = smem + (i % NSTG) * STAGE;
     // partial scores over this wave's dims: tile kt, lane (r = l15, g): image rows 16·kt + 4g … + 3
-    f32x4 sp[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-    for (int t = 0; t < KS; ++t)
+    for (int rt = 0; rt < RT; ++rt) {
+      f32x4 sp[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-        sp[kt] = emma(*reinterpret_cast<const u32x4*>(stage + soff[t] + 16 * kt * EROW), qf[t], sp[kt]);
+      for (int t = 0; t < KS; ++t)
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt) *reinterpret_cast<f32x4*>(sred + ((wave * 2 + kt) * 16 + l15) * 16 + 4 * g) = sp[kt];
-    __syncthreads();
-    f32x4 sv[2];
+        for (int kt = 0; kt < 2; ++kt)
+          sp[kt] = emma(*reinterpret_cast<const u32x4*>(stage + soff[t] + 16 * kt * EROW), qf[rt][t], sp[kt]);
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      sv[kt] = *reinterpret_cast<const f32x4*>(sred + (kt * 16 + l15) * 16 + 4 * g);
-#pragma unroll
-      for (int w = 1; w < 8; ++w) sv[kt] += *reinterpret_cast<const f32x4*>(sred + ((w * 2 + kt) * 16 + l15) * 16 + 4 * g);
+      for (int kt = 0; kt < 2; ++kt) *reinterpret_cast<f32x4*>(sred + rt * RED + ((wave * 2 + kt) * 16 + l15) * 16 + 4 * g) = sp[kt];
     }
+    __syncthreads();
     // image row 16·kt + 4g + e holds key 8g + 4·kt + e of the stage (xdma8<PERM>)
     const int kbase = (st_begin + i) * 32 + 8 * g;
-    float mx = -INFINITY;
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
+    for (int rt = 0; rt < RT; ++rt) {
+      const float* sr = sred + rt * RED;
+      f32x4 sv[2];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (kbase + 4 * kt + e >= Sb) sv[kt][e] = -INFINITY;
-        mx = fmaxf(mx, sv[kt][e]);
+      for (int kt = 0; kt < 2; ++kt) {
+        sv[kt] = *reinterpret_cast<const f32x4*>(sr + (kt * 16 + l15) * 16 + 4 * g);
+#pragma unroll
+        for (int w = 1; w < 8; ++w) sv[kt] += *reinterpret_cast<const f32x4*>(sr + ((w * 2 + kt) * 16 + l15) * 16 + 4 * g);
       }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);                 // finite: every stage of a range holds at least one key
-    const float alpha = __expf(m_run - m_new);
-    bf16x8 pf;
-    float ps = 0.f;
+      float mx = -INFINITY;
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
+      for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float pv = __expf(sv[kt][e] - m_new);
-        ps += pv;
-        pf[kt * 4 + e] = (bf16_t)pv;
+        for (int e = 0; e < 4; ++e) {
+          if (kbase + 4 * kt + e >= Sb) sv[kt][e] = -INFINITY;
+          mx = fmaxf(mx, sv[kt][e]);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run[rt], mx);             // finite: every stage of a range holds at least one key
+      const float alpha = __expf(m_run[rt] - m_new);
+      bf16x8 pf;
+      float ps = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float pv = __expf(sv[kt][e] - m_new);
+          ps += pv;
+          pf[kt * 4 + e] = (bf16_t)pv;
+        }
+      l_run[rt] = l_run[rt] * alpha + ps;
+      m_run[rt] = m_new;
+      const u32x4 pfrag = __builtin_bit_cast(u32x4, pf);
+#pragma unroll
+      for (int db = 0; db < NDB; ++db) {
+        const char* ap = stage + coff[db];
+        s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ap));
+        s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ap + 16 * EROW));
+        const u32x2 u0 = __builtin_bit_cast(u32x2, t0), u1 = __builtin_bit_cast(u32x2, t1);
+        cacc[rt][db] = emma(u32x4{u0[0], u0[1], u1[0], u1[1]}, pfrag, cacc[rt][db] * alpha);
       }
-    l_run = l_run * alpha + ps;
-    m_run = m_new;
-    const u32x4 pfrag = __builtin_bit_cast(u32x4, pf);
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) {
-      const char* ap = stage + coff[db];
-      s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ap));
-      s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ap + 16 * EROW));
-      const u32x2 u0 = __builtin_bit_cast(u32x2, t0), u1 = __builtin_bit_cast(u32x2, t1);
-      cacc[db] = emma(u32x4{u0[0], u0[1], u1[0], u1[1]}, pfrag, cacc[db] * alpha);
     }
   }
   // lane (r = l15, g): cacc[db][i] = Σ exp(s − m)·E[key][wave·D/8 + 16·db + 4g + i]
-  l_run += __shfl_xor(l_run, 16, 64);
-  l_run += __shfl_xor(l_run, 32, 64);
-  const int64_t pr = ((int64_t)z * a.B + b) * 16 + l15;
-  if (wave == 0 && g == 0) {
-    a.part_ml[pr * 2] = m_run;
-    a.part_ml[pr * 2 + 1] = l_run;
-  }
 #pragma unroll
-  for (int db = 0; db < NDB; ++db) *reinterpret_cast<f32x4*>(a.part_c + pr * D + wave * (D / 8) + db * 16 + 4 * g) = cacc[db];
+  for (int rt = 0; rt < RT; ++rt) {
+    float l = l_run[rt];
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    if (seq0 + rt >= a.K) continue;
+    const int64_t pr = (((int64_t)z * a.B + b) * a.K + seq0 + rt) * 16 + l15;
+    if (wave == 0 && g == 0) {
+      a.part_ml[pr * 2] = m_run[rt];
+      a.part_ml[pr * 2 + 1] = l;
+    }
+#pragma unroll
+    for (int db = 0; db < NDB; ++db) *reinterpret_cast<f32x4*>(a.part_c + pr * D + wave * (D / 8) + db * 16 + 4 * g) = cacc[rt][db];
+  }
 }
 
 // ctx[b][h][j] = (Σ_z w_z·C′_z[b][h][:] / Σ_z w_z·l_z)·Wv[h·64 + j][:],  w_z = exp(m_z − max_z m_z):  grid (H, B), 256 threads
@@ -1228,6 +1256,7 @@ static int xdecode_decide(const void* q, int64_t q_sb, int64_t q_ld, const void*
   a.e = (const char*)e; a.e_ld = e_ld; a.k_off = k_off;
   a.part_ml = part_ml; a.part_c = part_c;
   a.R = R; a.D = D; a.B = B; a.Z = key_splits;
+  a.K = 1; a.q_sk = 0;
   pl = xdecode_plan(D, B, key_splits);
   return LAKO_OK;
 }
@@ -1276,4 +1305,89 @@ extern "C" int lako_xattn_decode_combine(const float* part_ml, const float* part
   else hipLaunchKernelGGL((xdecode_combine_kernel<32>), grid, dim3(256), 0, (hipStream_t)stream, a);
   LAKO_LAUNCH_CHECK();
   return LAKO_OK;
+}
+
+// The multi-tile decode rule (K sequences per sample over one copy of its keys): xdecode_kernel<KS = D / 256, RT>, RT ∈ {4, 2, 1} row
+// tiles per workgroup.  XDM_RT_MAX[KS − 2] is the largest RT whose ring of >= 2 stages [32 keys × D] plus RT × 16 KiB of partial score
+// tiles fits 160 KiB of LDS AND whose instantiation the compiler builds without scratch memory (kernel-resource-usage remarks of
+// hipcc --offload-arch=gfx950; DESIGN.md §3 "Sampled decoding" has the table).  RT = the largest admitted value <= K, unless `rt`
+// forces one (measurements / tests: 0 = the rule); the K − RT·⌊K / RT⌋ sequences left over ride in a last, partly idle workgroup of
+// the third grid dimension.  The ring has three stages where they still fit next to the tiles, else two — the kernel derives the
+// same count from (D, RT).
+static constexpr int XDM_RT_MAX[3] = {4, 4, 2};      // D = 512, 768, 1024
+static lako_xattn_plan_t xdecode_multi_plan(int D, int B, int K, int key_splits, int rt_forced) {
+  lako_xattn_plan_t pl{};
+  const int stage_b = 32 * D * 2, red_b = 8 * 32 * 16 * 4;
+  int rt = XDM_RT_MAX[D / 256 - 2];
+  while (rt > K) rt >>= 1;
+  if (rt_forced) rt = rt_forced;
+  pl.kernel = LAKO_XK_DECODE_MULTI;
+  pl.ks = D / 256;
+  pl.nt = rt;
+  pl.stages = 3 * stage_b + rt * red_b <= 160 * 1024 ? 3 : 2;
+  pl.lds = pl.stages * stage_b + rt * red_b;
+  pl.gx = key_splits; pl.gy = B; pl.gz = (K + rt - 1) / rt;
+  pl.block = 512;
+  return pl;
+}
+
+static int xdecode_multi_decide(const void* q, int64_t q_sb, int64_t q_sk, int64_t q_ld, const void* e, int64_t e_ld, const int32_t* k_off,
+                                float* part_ml, float* part_c, int R, int D, int B, int K, int key_splits, int rt, XdArgs& a,
+                                lako_xattn_plan_t& pl) {
+  const char* fn = "lako_xattn_decode_multi";
+  pl = lako_xattn_plan_t{};
+  LAKO_CHECK_ARG(q && e && k_off && part_ml && part_c, "%s: null operand", fn);
+  LAKO_CHECK_ARG(R >= 1 && R <= 16 && (D == 512 || D == 768 || D == 1024) && B >= 1 && key_splits >= 1 && key_splits <= 64 &&
+                     e_ld % 8 == 0 && e_ld >= D && e_ld < (1 << 20) && q_ld % 8 == 0 && q_sb % 8 == 0 && q_sk % 8 == 0,
+                 "%s: R <= 16, D in {512, 768, 1024}, 1 <= key_splits <= 64, 16-byte rows (R=%d D=%d)", fn, R, D);
+  LAKO_CHECK_ARG(K >= 1 && K <= 65535 && (int64_t)B * K <= 0x7FFFFFFF / 16, "%s: 1 <= K <= 65535 sequences per sample (K=%d)", fn, K);
+  LAKO_CHECK_ARG(rt == 0 || ((rt == 1 || rt == 2 || rt == 4) && rt <= XDM_RT_MAX[D / 256 - 2]),
+                 "%s: rt=%d is not 0 (the rule) or a row-tile count the kernel is built for at D=%d", fn, rt, D);
+  XCHECK_ALIGN(fn, q, 16);
+  XCHECK_ALIGN(fn, e, 16);
+  XCHECK_ALIGN(fn, part_c, 16);
+  a = XdArgs{};
+  a.q = (const char*)q; a.q_sb = q_sb; a.q_sk = q_sk; a.q_ld = q_ld;
+  a.e = (const char*)e; a.e_ld = e_ld; a.k_off = k_off;
+  a.part_ml = part_ml; a.part_c = part_c;
+  a.R = R; a.D = D; a.B = B; a.Z = key_splits; a.K = K;
+  pl = xdecode_multi_plan(D, B, K, key_splits, rt);
+  return LAKO_OK;
+}
+
+extern "C" int lako_xattn_decode_multi(const void* q, int64_t q_sb, int64_t q_sk, int64_t q_ld, const void* e, int64_t e_ld,
+                                       const int32_t* k_off, float* part_ml, float* part_c, int R, int D, int B, int K, int key_splits,
+                                       int rt, lako_stream_t stream) {
+  XdArgs a;
+  lako_xattn_plan_t pl;
+  if (const int rc = xdecode_multi_decide(q, q_sb, q_sk, q_ld, e, e_ld, k_off, part_ml, part_c, R, D, B, K, key_splits, rt, a, pl)) return rc;
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy, (unsigned)pl.gz), block((unsigned)pl.block);
+  hipStream_t s = (hipStream_t)stream;
+#define XDM_GO(KSV, RTV)                                                                                               \
+  do {                                                                                                                 \
+    static lako_lds_cur_t done;                                                                                          \
+    xset_lds(reinterpret_cast<const void*>(&xdecode_kernel<KSV, RTV>), pl.lds, done);                                  \
+    hipLaunchKernelGGL((xdecode_kernel<KSV, RTV>), grid, block, pl.lds, s, a);                                         \
+  } while (0)
+#define XDM_KS(KSV, RT4)                                                                                               \
+  do {                                                                                                                 \
+    if (pl.nt == 1) XDM_GO(KSV, 1);                                                                                    \
+    else if (pl.nt == 2) XDM_GO(KSV, 2);                                                                               \
+    else XDM_GO(KSV, RT4);                                                                                             \
+  } while (0)
+  if (pl.ks == 2) XDM_KS(2, 4);
+  else if (pl.ks == 3) XDM_KS(3, 4);
+  else XDM_KS(4, 2);      // D = 1024: RT = 4 is refused above
+#undef XDM_KS
+#undef XDM_GO
+  LAKO_LAUNCH_CHECK();
+  return LAKO_OK;
+}
+
+extern "C" int lako_xattn_decode_multi_plan(const void* q, int64_t q_sb, int64_t q_sk, int64_t q_ld, const void* e, int64_t e_ld,
+                                            const int32_t* k_off, float* part_ml, float* part_c, int R, int D, int B, int K,
+                                            int key_splits, int rt, lako_xattn_plan_t* out) {
+  LAKO_CHECK_ARG(out != nullptr, "lako_xattn_decode_multi_plan: null out");
+  XdArgs a;
+  return xdecode_multi_decide(q, q_sb, q_sk, q_ld, e, e_ld, k_off, part_ml, part_c, R, D, B, K, key_splits, rt, a, *out);
 }

@@ -31,6 +31,9 @@ from .relpos import bucket_lut
 
 ALIGN = 64  # elements; keeps every block 256-B aligned in fp32 and 128-B aligned in bf16
 
+# generate(num_return_sequences=K): the one-pass cross-attention kernel (lako_xattn_decode_multi) up to this many sequences per question
+XDM_MAX_K = 2
+
 # dropout site ids (unique per place a torch.nn.Dropout sits in the reference graph)
 S_ENC_EMBED, S_ENC_FINAL, S_DEC_EMBED, S_DEC_FINAL = 1, 2, 3, 4
 
@@ -1377,16 +1380,57 @@ class Engine:
         self.ctx = None
 
     # ------------------------------------------------------------------------------------------
-    # greedy decode  (HF generate: num_beams=1, do_sample=False, use_cache=True)
+    # greedy decode  (HF generate: num_beams=1, do_sample=False, use_cache=True), and sampled decode (do_sample=True: temperature,
+    # top-k, top-p; num_return_sequences = K rows per question over ONE copy of the question's encoder states)
     # ------------------------------------------------------------------------------------------
-    def generate(self, input_ids, attention_mask, max_length: int, capture_scores: bool = False, lengths=None):
+    def generate(self, input_ids, attention_mask, max_length: int, capture_scores: bool = False, lengths=None, *, do_sample: bool = False,
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1, seed=None,
+                 return_scores: bool = False):
+        """Defaults: the greedy decode, int64 [B, <= max_length].  do_sample / return_scores switch the last launch of a step from
+        lako_greedy_step to lako_sample_step (greedy with scores: top_k = 1) and the decoder-side buffers to B·K rows, K =
+        num_return_sequences: row b·K + k is answer k of question b (HF's layout).  The encoder runs once for the B questions and its
+        states (or their K/V projections) are stored once; the K rows of a question are K query positions of its cross-attention.
+        return_scores adds float32 [B, K]: Σ over a row's emitted tokens (its EOS included, the pads after it not) of
+        log_softmax(raw logits)[token] — the model's own log-probability, what `score` returns for that sequence; HF's transition scores
+        are those of the PROCESSED distribution (temperature applied, truncated tokens at −∞), which say how likely the sampler was to
+        pick the token, not how likely the model finds the answer — the quantity a re-ranker wants is the latter."""
+        K, sampled = int(num_return_sequences), bool(do_sample or return_scores)
+        if not temperature > 0:
+            raise ValueError(f"temperature must be > 0, got {temperature}")
+        if not 0 < top_p <= 1:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError(f"top_k must be an integer >= 0, got {top_k}")
+        if K < 1:
+            raise ValueError(f"num_return_sequences must be >= 1, got {num_return_sequences}")
+        if K > 1 and not do_sample:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding has one answer per question")
+        if do_sample and capture_scores:
+            raise ValueError("do_sample=True while the cross-attention scores are captured: the capture belongs to the greedy decode")
+        if K > 1 and self.cfg.legacy_cross_bias:
+            raise ValueError("num_return_sequences > 1 is not implemented with legacy_cross_bias")
         if self.shadows_stale:
             self.refresh_shadows()
         cfg, ops = self.cfg, self.ops
         B, N, L = input_ids.shape
         d, f, inner, H, V = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads, cfg.vocab_size
         S, Ld, eps, dk = N * L, cfg.num_decoder_layers, cfg.layer_norm_epsilon, cfg.d_kv
-        ws = self._workspace(("gen", B, N, L, max_length))
+        BK = B * K                     # decoder rows
+        ws = self._workspace(("gen", B, N, L, max_length) + ((K, "s") if sampled else ()))
+        if sampled:
+            # the sampler's settings live in device memory at a stable address (the kernel reads them: captured steps replay unchanged
+            # under other settings); the step index is an argument baked into each step's graph, as `pos` is
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # torch's global (host) generator
+            seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            words = np.array([np.float32(temperature).view(np.uint32), np.float32(top_p).view(np.uint32),
+                              (min(int(top_k), 0x7FFFFFFF) if do_sample else 1), seed & 0xFFFFFFFF, seed >> 32, 0, 0, 0], dtype=np.uint32)
+            sparams = self._buf(ws, "g.sparams", (8,), torch.int32)
+            if "g.sparams_host" not in ws:       # pinned: the upload is an enqueue like every other launch of the call
+                ws["g.sparams_host"] = torch.zeros(8, dtype=torch.int32).pin_memory() if torch.cuda.is_available() else \
+                    torch.zeros(8, dtype=torch.int32)
+            ws["g.sparams_host"].copy_(torch.from_numpy(words.view(np.int32)))      # (the last call ended with a wait on its last step)
+            sparams.copy_(ws["g.sparams_host"], non_blocking=True)
         ids = input_ids.reshape(-1).contiguous()
         mask_u8 = attention_mask.reshape(B * N, L).to(torch.uint8).contiguous()
         # valid tokens only (as in forward_loss) unless the raw scores are captured: those are laid out per padded position
@@ -1411,31 +1455,41 @@ class Engine:
         use_graph = self.device.type == "cuda" and not capture_scores and getattr(ops, "probe", None) is None and \
             os.environ.get("LAKO_GEN_GRAPH", "1") != "0"
         use_x = os.environ.get("LAKO_XATTN_GENERATE", "1" if use_graph else "0") == "1" and not capture_scores
-        xa = self._xattn_plan(rag, B, N, L, H) if use_x else None
+        xa = self._xattn_plan(rag, B, N, L, K * H) if use_x else None
         self.xattn_active = xa is not None
         enc_out, kv = self._encode(ws, ids, self._enc_mask(rag, mask_u8), B * N, L, 0.0, 0, save=False, rag=rag, want_kv=xa is None)
         if xa is not None:
+            # (the K sequences of a question: K·H query rows of its sample — the unfused kernels take any row count, the one-pass
+            # kernel carries them as 16-row tiles, several per workgroup: lako_xattn_decode_multi)
             mode += "x"
             cap = B * (-(-S // 256) * 256)
             xoff = self._buf(ws, "g.xoff", (2, B + 1), torch.int32)
             xoff[0].copy_(xa.k_off)
             xoff[1].copy_(xa.p_off)
-            xq = self._buf(ws, "g.xq", (B, H, d))
-            xs = self._buf(ws, "g.xs", (H, cap), torch.float32)      # launched over all `cap` columns: tiles past the batch's
-            xp = self._buf(ws, "g.xp", (H, cap))                      # last key column exit at once
-            xst = self._buf(ws, "g.xst", (B, H, 2), torch.float32)
-            xc = self._buf(ws, "g.xc", (xa.splits, B, H, d), torch.float32)
+            xq = self._buf(ws, "g.xq", (B, K * H, d))
+            xs = self._buf(ws, "g.xs", (K * H, cap), torch.float32)      # launched over all `cap` columns: tiles past the batch's
+            xp = self._buf(ws, "g.xp", (K * H, cap))                      # last key column exit at once
+            xst = self._buf(ws, "g.xst", (B, K * H, 2), torch.float32)
+            xc = self._buf(ws, "g.xc", (xa.splits, B, K * H, d), torch.float32)
             # scores, softmax and context of a decode step in one pass over the encoder states when the shapes allow
-            fused = dk == 64 and getattr(ops, "xattn_decode_ok", lambda *_: False)(H, d) and os.environ.get("LAKO_XATTN_DECODE", "1") != "0"
+            # (K > 1: only up to XDM_MAX_K sequences per question — above, the unfused kernels' K·H-row MFMA tiles beat the one-pass
+            # kernel's row tiles although they read E twice: DESIGN.md §3 "Sampled decoding"; LAKO_XATTN_DECODE=1 forces the one pass)
+            xd = os.environ.get("LAKO_XATTN_DECODE")
+            fused = dk == 64 and getattr(ops, "xattn_decode_ok", lambda *_: False)(H, d) and xd != "0" and (K <= XDM_MAX_K or xd == "1")
             if fused:
-                zd = max(1, min(64, 256 // B))
-                pml = self._buf(ws, "g.xpml", (zd, B, 16, 2), torch.float32)
-                pc = self._buf(ws, "g.xpc", (zd, B, 16, d), torch.float32)
+                # (≈256 workgroups: a workgroup carries as many of a question's sequences as the library's plan gives it row tiles)
+                tiles = getattr(ops, "xattn_decode_multi_tiles", lambda d_, k_: min(4, k_))(d, K)
+                zd = max(1, min(64, 256 // (B * -(-K // tiles))))
+                pml = self._buf(ws, "g.xpml", (zd, BK, 16, 2), torch.float32)
+                pc = self._buf(ws, "g.xpc", (zd, BK, 16, d), torch.float32)
                 mode += "f"
+        if sampled:
+            mode += f"s{K}"
         ML = max_length
-        seq = self._buf(ws, "g.seq", (B, ML), torch.int64)
-        nxt = self._buf(ws, "g.next", (B,), torch.int64)
-        done = self._buf(ws, "g.done", (B,), torch.uint8)
+        seq = self._buf(ws, "g.seq", (BK, ML), torch.int64)
+        nxt = self._buf(ws, "g.next", (BK,), torch.int64)
+        done = self._buf(ws, "g.done", (BK,), torch.uint8)
+        score = self._buf(ws, "g.score", (BK,), torch.float32) if sampled else None
         # finished-row count after every step, mirrored to pinned host memory: the host looks at the count of step t − LAG
         # (an event wait on that step only), so it keeps enqueueing LAG steps ahead of the GPU instead of draining the queue
         # after every token; the LAG extra steps a finished batch may run emit pad for every row and are cut off below
@@ -1444,7 +1498,7 @@ class Engine:
             ws["g.ndone_host"] = torch.zeros(ML, dtype=torch.int32).pin_memory() if torch.cuda.is_available() else \
                 torch.zeros(ML, dtype=torch.int32)
         ndone_host, LAG, events = ws["g.ndone_host"], 2, []
-        for t_ in (seq, nxt, done, ndone):
+        for t_ in (seq, nxt, done, ndone) + ((score,) if sampled else ()):
             ops.zero_(t_)                                  # decoder_start_token_id = pad = 0
         rel = self._buf(ws, "g.rel", (H, 2 * ML - 1), torch.float32)
         ops.relpos_expand(self.dec_rel.p, self._lut(ML, ML, False), rel)
@@ -1457,15 +1511,16 @@ class Engine:
             ops.relpos_expand(self.dec_xrel.p, self._lut(ML, ML, False), xrel)
         # per layer [B, max_length, (q | k | v)]: ONE projection GEMM per step writes the step's q, k and v into row t; q is read
         # back from there, k and v stay as the cache
-        cache = [self._buf(ws, f"g.cache.{i}", (B, ML, 3 * inner)) for i in range(Ld)]
+        cache = [self._buf(ws, f"g.cache.{i}", (BK, ML, 3 * inner)) for i in range(Ld)]
         scores = self._buf(ws, "g.scores", (Ld, B, H, 1, S), torch.float32) if capture_scores else None
-        h, h1, h2, xn = (self._buf(ws, f"g.{n}", (B, d)) for n in ("h", "h1", "h2", "xn"))
-        rs = self._buf(ws, "g.rs", (B,), torch.float32)
-        c1, qc, c2 = (self._buf(ws, f"g.{n}", (B, inner)) for n in ("c1", "qc", "c2"))
-        st = self._buf(ws, "g.st", (B, H, 1, 4), torch.float32)
-        a1 = self._buf(ws, "g.a1", (B, f))
-        pre = self._buf(ws, "g.pre", (B, 2 * f)) if cfg.gated else None
-        logits = self._buf(ws, "g.logits", (B, V), torch.float32)
+        h, h1, h2, xn = (self._buf(ws, f"g.{n}", (BK, d)) for n in ("h", "h1", "h2", "xn"))
+        rs = self._buf(ws, "g.rs", (BK,), torch.float32)
+        c1, qc, c2 = (self._buf(ws, f"g.{n}", (BK, inner)) for n in ("c1", "qc", "c2"))
+        st = self._buf(ws, "g.st", (BK, H, 1, 4), torch.float32)
+        stx = self._buf(ws, "g.stx", (B, H, K, 4), torch.float32) if K > 1 else st      # the cross-attention's: K query positions per sample
+        a1 = self._buf(ws, "g.a1", (BK, f))
+        pre = self._buf(ws, "g.pre", (BK, 2 * f)) if cfg.gated else None
+        logits = self._buf(ws, "g.logits", (BK, V), torch.float32)
         def step(t):
             """enqueue decode step t (reads nxt, writes seq[:, t + 1], nxt, done, ndone[t])"""
             ops.embed_fwd(nxt, self.shared.w, h)
@@ -1475,14 +1530,14 @@ class Engine:
             for i in range(Ld):
                 lw = self.dec[i]
                 if fz:
-                    ops.gemm_nt(h, lw["qkv"].w, cache[i].view(B, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner], **nrm(lw["ln1"].p))
+                    ops.gemm_nt(h, lw["qkv"].w, cache[i].view(BK, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner], **nrm(lw["ln1"].p))
                 else:
                     ops.rmsnorm_fwd(h, lw["ln1"].p, xn, rs, eps)
-                    ops.gemm_nt(xn, lw["qkv"].w, cache[i].view(B, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner])
+                    ops.gemm_nt(xn, lw["qkv"].w, cache[i].view(BK, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner])
                 qs = cache[i][:, t:t + 1, :inner].unflatten(2, (H, dk))
                 kc = cache[i][:, :t + 1, inner:2 * inner].unflatten(2, (H, dk))
                 vc = cache[i][:, :t + 1, 2 * inner:].unflatten(2, (H, dk))
-                ops.attn_fwd(qs, kc, vc, c1.view(B, 1, H, dk), st, rel_bias=rel, rel_off=ML - 1 - t)
+                ops.attn_fwd(qs, kc, vc, c1.view(BK, 1, H, dk), st, rel_bias=rel, rel_off=ML - 1 - t)
                 ops.gemm_nt(c1, lw["o"].w, h1, resid=h)
                 if fz:
                     ops.gemm_nt(h1, lw["cq"].w, qc, **nrm(lw["ln2"].p))
@@ -1490,20 +1545,23 @@ class Engine:
                     ops.rmsnorm_fwd(h1, lw["ln2"].p, xn, rs, eps)
                     ops.gemm_nt(xn, lw["cq"].w, qc)
                 if xa is None:
-                    ops.attn_fwd(qc.view(B, 1, H, dk), self._heads(kv, kb, kt, 2 * i * inner),
-                                 self._heads(kv, kb, kt, (2 * i + 1) * inner), c2.view(B, 1, H, dk), st,
+                    ops.attn_fwd(qc.view(B, K, H, dk), self._heads(kv, kb, kt, 2 * i * inner),
+                                 self._heads(kv, kb, kt, (2 * i + 1) * inner), c2.view(B, K, H, dk), stx,
                                  scores_out=scores[i] if (capture_scores and t == 0) else None, **xkw)
                 else:
-                    ops.headbatch_nt(qc.view(B, 1, H, dk), self._xw(i, "k", transposed=True), xq.view(B, 1, H, d))
+                    ops.headbatch_nt(qc.view(B, K, H, dk), self._xw(i, "k", transposed=True), xq.view(B, K, H, d))
                     if fused:
-                        ops.xattn_decode(xq, enc_out, xoff[0], pml, pc)
+                        if K == 1:
+                            ops.xattn_decode(xq, enc_out, xoff[0], pml, pc)
+                        else:
+                            ops.xattn_decode_multi(xq.view(B, K, H, d), enc_out, xoff[0], pml, pc)
                         r0 = (2 * i + 1) * inner
                         ops.xattn_decode_combine(pml, pc, self.kv_all.w[r0:r0 + inner], c2, H)
                     else:
                         ops.xattn_scores(xq, enc_out, xoff[0], xoff[1], cap, xs)
-                        ops.xattn_softmax_fwd(xs, xst, xp, xoff[0], xoff[1], 1, H, S)
+                        ops.xattn_softmax_fwd(xs, xst, xp, xoff[0], xoff[1], K, H, S)
                         ops.xattn_context(xp, enc_out, xoff[0], xoff[1], xc)
-                        ops.headbatch_nt(xc.view(xa.splits, B, 1, H, d), self._xw(i, "v"), c2.view(B, 1, H, dk))
+                        ops.headbatch_nt(xc.view(xa.splits, B, K, H, d), self._xw(i, "v"), c2.view(B, K, H, dk))
                 ops.gemm_nt(c2, lw["co"].w, h2, resid=h1)
                 out1, act = (pre, {}) if cfg.gated else (a1, dict(relu=True))
                 if fz:
@@ -1516,7 +1574,10 @@ class Engine:
                 ops.gemm_nt(a1, lw["wo"].w, h, resid=h2)
             ops.rmsnorm_fwd(h, self.dec_final.p, xn, rs, eps)
             ops.gemm_nt(xn, self.lm_head.w, logits, alpha=self.head_alpha)
-            ops.greedy_step(logits, seq, t + 1, nxt, done, ndone[t:t + 1], cfg.eos_token_id, cfg.pad_token_id)
+            if sampled:
+                ops.sample_step(logits, seq, t + 1, nxt, done, score, ndone[t:t + 1], sparams, t, K, cfg.eos_token_id, cfg.pad_token_id)
+            else:
+                ops.greedy_step(logits, seq, t + 1, nxt, done, ndone[t:t + 1], cfg.eos_token_id, cfg.pad_token_id)
 
         # A decode step is ≈130 dependent launches of a few µs each: the host's launch rate bounds the loop.  After one eager call
         # per (shape, mode) — the kernels' one-time setup must not happen under capture — every step position is captured ONCE into a
@@ -1555,12 +1616,13 @@ class Engine:
             if look >= 0:
                 if ndone.is_cuda:
                     events[look].synchronize()
-                first = next((u for u in range(max(look - LAG, 0), look + 1) if int(ndone_host[u]) == B), None)
+                first = next((u for u in range(max(look - LAG, 0), look + 1) if int(ndone_host[u]) == BK), None)
                 if first is not None:        # HF stops right after the step in which the last row emitted EOS
                     n_out = first + 2
                     break
         out = seq[:, :n_out].clone()
         if capture_scores:
             # [B, H, n_layers, S] — the layout get_crossattention_scores builds with torch.cat(dim=2), src/model.py:152-160
-            return out, scores[:, :, :, 0, :].permute(1, 2, 0, 3).contiguous()
-        return out
+            cs = scores[:, :, :, 0, :].permute(1, 2, 0, 3).contiguous()
+            return (out, cs, score.view(B, K).clone()) if return_scores else (out, cs)
+        return (out, score.view(B, K).clone()) if return_scores else out

@@ -216,15 +216,34 @@ class FiDT5(nn.Module):
         return FiDOutput(loss, logits)
 
     @torch.no_grad()
-    def generate(self, input_ids, attention_mask, max_length, passage_lengths=None):
-        """src/model.py:54-60 → greedy decode, int64 [B, ≤max_length] with the leading start token."""
+    def generate(self, input_ids, attention_mask, max_length, passage_lengths=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
+                 num_return_sequences=1, seed=None, return_scores=False):
+        """src/model.py:54-60 → greedy decode, int64 [B, ≤max_length] with the leading start token.
+
+        The sampling arguments of HF `generate` (extension; the defaults are the greedy decode above, launch for launch):
+        `do_sample=True` draws every token from softmax(logits / temperature) after the top-k (0 = off) and nucleus (top_p) truncations,
+        `num_return_sequences=K` returns int64 [B·K, ≤max_length] with question b's answers in rows b·K … b·K+K−1 (HF's layout; pad after a
+        row's EOS; the call ends after the step in which the last row emitted EOS).  The encoder runs once for the B questions; only the
+        decoder side has B·K rows.  `seed` (int; None draws one from torch's global generator) fixes the tokens: the draw of answer k at
+        step t is a hash of (seed, k, t), so the same seed, inputs and weights give the same tokens eagerly and under graph replay, and a
+        question's answers do not depend on what else is in the batch.  (The three cross-attention routes are the same mathematics; in fp32
+        they draw the same tokens, in bf16 their logits round differently and a draw near a CDF edge can fall on either side.)  `top_k=1` makes every row the greedy decode.
+        `return_scores=True` returns (tokens, scores float32 [B, K]): the sum over a row's emitted tokens (EOS included, pads not) of
+        log_softmax(raw logits)[token] — what `score` returns for that sequence.  Unlike HF's transition scores it is the model's own
+        log-probability: temperature and truncation shape which token is drawn, not the score.  Works with do_sample=False (K = 1) too.
+        ValueError: temperature ≤ 0, top_p outside (0, 1], top_k < 0, K < 1, K > 1 without do_sample, do_sample while cross-attention
+        scores are captured, K > 1 with legacy_cross_bias."""
         self.n_passages = input_ids.size(1)
         eng = self._get_engine()
+        skw = {}
+        if do_sample or return_scores or num_return_sequences != 1 or temperature != 1.0 or top_k != 0 or top_p != 1.0:
+            skw = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, num_return_sequences=num_return_sequences,
+                       seed=seed, return_scores=return_scores)
         if self._capture_scores and self._score_storage is None:
-            out, scores = eng.generate(input_ids, attention_mask, max_length, capture_scores=True)
+            out, scores, *rest = eng.generate(input_ids, attention_mask, max_length, capture_scores=True, **skw)
             self._score_storage = scores
-            return out
-        return eng.generate(input_ids, attention_mask, max_length, lengths=passage_lengths)
+            return (out, rest[0]) if rest else out
+        return eng.generate(input_ids, attention_mask, max_length, lengths=passage_lengths, **skw)
 
     @torch.no_grad()
     def score(self, input_ids, attention_mask, candidates, passage_lengths=None, normalize=False, candidate_chunk=None):

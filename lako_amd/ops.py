@@ -678,6 +678,42 @@ class HipOps:
         check(self.lib.lako_xattn_decode_plan(*self._xattn_decode_args(Q, E, k_off, part_ml, part_c), C.byref(plan)), "lako_xattn_decode_plan")
         return plan
 
+    @staticmethod
+    def xattn_decode_multi_tiles(d_model, K):
+        """row tiles (sequences of one sample) a workgroup of lako_xattn_decode_multi carries: the plan rule of csrc/xattn.hip
+        (XDM_RT_MAX: 4 at D = 512 / 768, 2 at D = 1024; the largest of 4 | 2 | 1 that is <= K) — for sizing the key ranges before the
+        buffers a plan query needs exist; tests/test_sample_plan_cpu.py holds it against lako_xattn_decode_multi_plan"""
+        rt = 2 if d_model == 1024 else 4
+        while rt > K:
+            rt >>= 1
+        return rt
+
+    @staticmethod
+    def _xattn_decode_multi_args(Q, E, k_off, part_ml, part_c, rt):
+        """the arguments of lako_xattn_decode_multi / lako_xattn_decode_multi_plan up to the stream / the plan"""
+        Bz, K, R, D = Q.shape
+        Z = part_c.shape[0]
+        if part_c.shape != (Z, Bz * K, 16, D) or part_ml.shape != (Z, Bz * K, 16, 2) or not part_c.is_contiguous() or \
+                not part_ml.is_contiguous() or Q.stride(3) != 1 or E.stride(1) != 1 or E.shape[1] != D:
+            raise LakoError(f"xattn_decode_multi: shapes Q{tuple(Q.shape)} E{tuple(E.shape)} part{tuple(part_c.shape)}")
+        return (_p(Q), Q.stride(0), Q.stride(1), Q.stride(2), _p(E), E.stride(0), _p(k_off), _p(part_ml), _p(part_c), R, D, Bz, K, Z, int(rt))
+
+    def xattn_decode_multi(self, Q, E, k_off, part_ml, part_c, rt=0):
+        """xattn_decode for K sequences per sample over the sample's one set of keys: Q [B, K, R <= 16, D] bf16 view, part_ml
+        [Z, B·K, 16, 2] / part_c [Z, B·K, 16, D] fp32 (contiguous) — per sequence the bits xattn_decode writes for its queries alone;
+        a workgroup carries `rt` sequences through one pass over its keys (0: the library's rule picks)"""
+        args = self._xattn_decode_multi_args(Q, E, k_off, part_ml, part_c, rt)
+        self._timed("xattn", 4.0 * args[9] * args[10] * args[12] * E.shape[0],
+                    lambda: check(self.lib.lako_xattn_decode_multi(*args, self._stream()), "lako_xattn_decode_multi"))
+
+    def xattn_decode_multi_plan(self, Q, E, k_off, part_ml, part_c, rt=0):
+        """the launch xattn_decode_multi would make for these arguments (lako_xattn_decode_multi_plan: nothing launched)"""
+        from ._lib import XattnPlan
+        plan = XattnPlan()
+        check(self.lib.lako_xattn_decode_multi_plan(*self._xattn_decode_multi_args(Q, E, k_off, part_ml, part_c, rt), C.byref(plan)),
+              "lako_xattn_decode_multi_plan")
+        return plan
+
     def xattn_decode_combine(self, part_ml, part_c, Wv, ctx, H):
         """ctx [B, H·64] bf16 = (merged ranges of xattn_decode)·Wvᵀ per head; Wv [H·64, D] bf16 rows of the V projection"""
         Z, Bz, _, D = part_c.shape
@@ -928,3 +964,15 @@ class HipOps:
         B, V = logits.shape
         self._timed("greedy_step", 0.0, lambda: check(self.lib.lako_greedy_step(_p(logits), V, B, _p(seq), seq.stride(0), int(pos), _p(next_ids), _p(done),
                                         _p(n_done), int(eos_id), int(pad_id), self._stream()), "lako_greedy_step"))
+
+    def sample_step(self, logits, seq, pos, next_ids, done, score, n_done, params, step, group, eos_id=1, pad_id=0):
+        """one sampled decode step (lako_sample_step): logits fp32 [rows, V] contiguous; params int32 [8] on the device (temperature and
+        top_p as float bits, top_k, the seed's two words); row r is sequence r % group of its question; score fp32 [rows] or None"""
+        rows, V = logits.shape
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or params.dtype != torch.int32 or params.numel() < 8 or \
+                seq.shape[0] != rows or next_ids.numel() != rows or done.numel() != rows or (score is not None and (
+                    score.dtype != torch.float32 or score.numel() != rows or not score.is_contiguous())):
+            raise LakoError("sample_step: logits fp32 [rows, V] contiguous, params int32 [8], seq / next_ids / done / score of `rows` rows")
+        self._timed("sample_step", 0.0, lambda: check(self.lib.lako_sample_step(
+            _p(logits), V, rows, int(group), _p(seq), seq.stride(0), int(pos), _p(next_ids), _p(done), _p(score), _p(n_done), _p(params),
+            int(step), int(eos_id), int(pad_id), self._stream()), "lako_sample_step"))
