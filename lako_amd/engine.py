@@ -162,9 +162,86 @@ class _XPlan:
     sub: dict = None        # {n chains: [per-chain _XPlan]} (column offsets relative to the chain's window)
 
 
+class _GenState:
+    """The state of one `generate` call: the `g.*` workspace buffers, all at stable addresses (the decode steps are captured into HIP
+    graphs), and the call's choices — mode (the graph cache's key), fused (the one-pass cross-attention kernel), K sequences per question,
+    BK decoder rows, ML = max_length, keys = the cross-attention's key descriptor over the stable copies.  Building it enqueues the
+    zeroing of the token state and the expansion of the position tables.  Read by Engine._gen_step / _gen_cross / _gen_drive."""
+
+    def __init__(self, eng, ws, bt, enc_out, kv, ML, K, sampled, capture, sparams):
+        cfg, ops = eng.cfg, eng.ops
+        d, f, inner, H, V, Ld, dk = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads, cfg.vocab_size, cfg.num_decoder_layers, cfg.d_kv
+        B, S, BK, xa = bt.B, bt.N * bt.L, bt.B * K, bt.xa
+        buf = lambda name, shape, dtype=None: eng._buf(ws, "g." + name, shape, dtype)       # noqa: E731
+        self.ws, self.B, self.K, self.BK, self.ML, self.S, self.sampled, self.capture = ws, B, K, BK, ML, S, sampled, capture
+        self.sparams, self.enc_out, self.kv, self.xa, self.fused = sparams, enc_out, kv, xa, False
+        # what changes from call to call is COPIED into workspace buffers (stable addresses: the decode steps are captured into HIP
+        # graphs): the samples' key offsets of the unpadded batch, or the key mask of the padded one
+        if bt.rag is None:
+            stable, self.mode = buf("kmask", (B, S), torch.uint8), "p"
+            stable.copy_(bt.mask_u8.view(B, S))
+        else:
+            stable, self.mode = buf("koff", (B + 1,), torch.int32), "r"
+            stable.copy_(bt.rag.soff)
+        self.keys = eng._cross_keys(bt, stable)
+        if xa is not None:
+            # (the K sequences of a question: K·H query rows of its sample — the unfused kernels take any row count, the one-pass
+            # kernel carries them as 16-row tiles, several per workgroup: lako_xattn_decode_multi)
+            self.mode += "x"
+            self.cap = B * (-(-S // 256) * 256)
+            self.xoff = buf("xoff", (2, B + 1), torch.int32)
+            self.xoff[0].copy_(xa.k_off)
+            self.xoff[1].copy_(xa.p_off)
+            self.xq = buf("xq", (B, K * H, d))
+            self.xs = buf("xs", (K * H, self.cap), torch.float32)      # launched over all `cap` columns: tiles past the batch's
+            self.xp = buf("xp", (K * H, self.cap))                      # last key column exit at once
+            self.xst = buf("xst", (B, K * H, 2), torch.float32)
+            self.xc = buf("xc", (xa.splits, B, K * H, d), torch.float32)
+            # scores, softmax and context of a decode step in one pass over the encoder states when the shapes allow
+            # (K > 1: only up to XDM_MAX_K sequences per question — above, the unfused kernels' K·H-row MFMA tiles beat the one-pass
+            # kernel's row tiles although they read E twice: DESIGN.md §3 "Sampled decoding"; LAKO_XATTN_DECODE=1 forces the one pass)
+            xd = os.environ.get("LAKO_XATTN_DECODE")
+            self.fused = dk == 64 and getattr(ops, "xattn_decode_ok", lambda *_: False)(H, d) and xd != "0" and (K <= XDM_MAX_K or xd == "1")
+            if self.fused:
+                # (≈256 workgroups: a workgroup carries as many of a question's sequences as the library's plan gives it row tiles)
+                tiles = getattr(ops, "xattn_decode_multi_tiles", lambda d_, k_: min(4, k_))(d, K)
+                zd = max(1, min(64, 256 // (B * -(-K // tiles))))
+                self.pml, self.pc = buf("xpml", (zd, BK, 16, 2), torch.float32), buf("xpc", (zd, BK, 16, d), torch.float32)
+                self.mode += "f"
+        if sampled:
+            self.mode += f"s{K}"
+        self.seq, self.nxt, self.done = buf("seq", (BK, ML), torch.int64), buf("next", (BK,), torch.int64), buf("done", (BK,), torch.uint8)
+        self.score = buf("score", (BK,), torch.float32) if sampled else None
+        # finished-row count after every step, mirrored to pinned host memory: the host looks at the count of step t − LAG
+        # (an event wait on that step only), so it keeps enqueueing LAG steps ahead of the GPU instead of draining the queue
+        # after every token; the LAG extra steps a finished batch may run emit pad for every row and are cut off by the driver
+        self.ndone = buf("ndone", (ML,), torch.int32)
+        if "g.ndone_host" not in ws or ws["g.ndone_host"].numel() < ML:
+            ws["g.ndone_host"] = torch.zeros(ML, dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        self.ndone_host = ws["g.ndone_host"]
+        for t_ in (self.seq, self.nxt, self.done, self.ndone) + ((self.score,) if sampled else ()):
+            ops.zero_(t_)                                  # decoder_start_token_id = pad = 0
+        self.rel = eng._rel_table(ws, "g.rel", eng.dec_rel, ML)
+        # legacy_cross_bias (_legacy_layout).  Step t's query sits at position t: table index key − t + ML − 1.  With score capture the
+        # reference runs ITS cross-attention forward (src/model.py:286-349), which sizes the bias by the step's own query length —
+        # 1 under the key / value cache — so every step sees the bias of position 0: one constant per head (src/model.py:323-325)
+        self.xrel = eng._rel_table(ws, "g.xrel", eng.dec_xrel, ML) if eng.dec_xrel is not None else None
+        # per layer [B, max_length, (q | k | v)]: ONE projection GEMM per step writes the step's q, k and v into row t; q is read
+        # back from there, k and v stay as the cache
+        self.cache = [buf(f"cache.{i}", (BK, ML, 3 * inner)) for i in range(Ld)]
+        self.scores = buf("scores", (Ld, B, H, 1, S), torch.float32) if capture else None
+        self.h, self.h1, self.h2, self.xn = (buf(n, (BK, d)) for n in ("h", "h1", "h2", "xn"))
+        self.c1, self.qc, self.c2 = (buf(n, (BK, inner)) for n in ("c1", "qc", "c2"))
+        self.rs, self.st = buf("rs", (BK,), torch.float32), buf("st", (BK, H, 1, 4), torch.float32)
+        self.stx = buf("stx", (B, H, K, 4), torch.float32) if K > 1 else self.st      # the cross-attention's: K query positions per sample
+        self.a1, self.pre = buf("a1", (BK, f)), (buf("pre", (BK, 2 * f)) if cfg.gated else None)
+        self.logits = buf("logits", (BK, V), torch.float32)
+
+
 @dataclass
 class _Ctx:
-    """What forward leaves behind for backward."""
+    """One [B, N, L] batch as the encoder and the cross-attention take it (Engine._batch fills B, N, L, ids, mask_u8, enc_mask, rag, xa and
+    enc_ids: all that score and generate need); forward_loss adds the rest: what it leaves behind for backward."""
     B: int = 0
     N: int = 0
     L: int = 0
@@ -175,11 +252,11 @@ class _Ctx:
     mask_u8: torch.Tensor = None
     enc_mask: torch.Tensor = None      # the ENCODER's key mask: mask_u8, or None when the batch has no padding at all (Engine._enc_mask)
     labels: torch.Tensor = None
-    dec_ids: torch.Tensor = None
     ckpt: bool = False
     rag: object = None      # _Ragged: the encoder ran on the valid tokens only
     xa: object = None       # _XPlan: cross-attention ran in the encoder-state space
     chains: list = None     # the decoder's sample chains (_dec_chains)
+    cross: tuple = None     # (kb, kt, ckw): the cross-attention's key descriptor the chains were built from (_cross_keys)
     enc_ids: torch.Tensor = None   # the encoder's token ids: all [B·N·L], or the valid ones when rag is set
     ws: dict = field(default_factory=dict)
 
@@ -607,6 +684,37 @@ class Engine:
         self.ops.pack_ids(ids_flat, rag.off, out, L)
         return out
 
+    def _batch(self, ws, input_ids, attention_mask, lengths, rows_q=None, T=None, keep_padding=False, p=0.0, seed=0, save=False):
+        """The prologue of forward_loss, score and generate: flat ids and uint8 mask, the unpadded layout when the mask allows it, the
+        cross-attention plan, the encoder pass (p, seed, save: _encode) → (batch, enc_out, kv).  Sets `_row_cap` and `xattn_active`.
+        rows_q: query rows per sample of the encoder-state cross-attention (_xattn_plan); None: no such plan, projected K / V.
+        T: the decoder length `_legacy_layout` compares the first passages with; None: the caller has no legacy bias.
+        keep_padding: the padded layout whatever the mask looks like (generate's captured scores are laid out per padded position);
+        nothing is then known about the mask's padding: `_all_valid` is cleared and _enc_mask keeps the mask."""
+        B, N, L = input_ids.shape
+        ids = input_ids.reshape(-1).contiguous()
+        mask_u8 = attention_mask.reshape(B * N, L).to(torch.uint8).contiguous()
+        rag = None if keep_padding else self._ragged_batch(attention_mask, B, N, L, lengths)
+        if keep_padding:
+            self._all_valid = False
+        elif T is not None:
+            rag = self._legacy_layout(rag, T)
+        self._row_cap = {rag.M: B * N * L} if rag is not None else {}
+        enc_ids = ids if rag is None else self._packed_ids(ws, ids, rag, L)
+        xa = self._xattn_plan(rag, B, N, L, rows_q) if rows_q is not None else None
+        self.xattn_active = xa is not None         # (bench.py / tests: which formulation the last call ran)
+        bt = _Ctx(B=B, N=N, L=L, ids=ids, mask_u8=mask_u8, enc_mask=self._enc_mask(rag, mask_u8), rag=rag, xa=xa, enc_ids=enc_ids, ws=ws)
+        return (bt,) + self._encode(ws, enc_ids, bt.enc_mask, B * N, L, p, seed, save=save, rag=rag, want_kv=xa is None)
+
+    @staticmethod
+    def _cross_keys(bt, stable=None):
+        """(kb, kt, ckw): how the cross-attention finds a sample's keys — [B, N·L] with the padding mask, or ONE run of packed valid tokens
+        with the samples' row offsets.  `stable`: generate's workspace copy of the mask / the offsets (captured graphs read that address)."""
+        S = bt.N * bt.L
+        if bt.rag is None:
+            return bt.B, S, dict(key_mask=bt.mask_u8.view(bt.B, S) if stable is None else stable)
+        return 1, bt.rag.M, dict(k_off=bt.rag.soff if stable is None else stable, max_k=S)
+
     def _check_lengths(self, attention_mask, lens_h, B, N, L):
         """`passage_lengths` must describe the mask (valid tokens first, exactly lengths[b, n] of them): anything else would pack the
         wrong tokens without a sign.  Every batch's mask is therefore compared with the uploaded lengths ON THE DEVICE (round 6: on by
@@ -808,7 +916,7 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     # the decoder as independent chains of samples
     # ------------------------------------------------------------------------------------------
-    def _dec_chains(self, B, T, p, seed, xa, xb, rag, kb, kt, ckw):
+    def _dec_chains(self, B, T, p, seed, xa, xb, rag, kb, kt, ckw, n=None):
         """The decoder of a training step is ≈400 launches on B·T ≈ 128 rows: each kernel is a few µs of launch ramp, dependent
         round trips and drain, and on one stream they run strictly one after the other.  Nothing in the decoder couples two samples
         (self- and cross-attention are per sample, everything else per row), so the batch can be cut into `LAKO_DEC_CHAINS` runs of
@@ -817,8 +925,9 @@ class Engine:
         1 chain 40.95 ms per step, 2 chains 42.0, 4 chains 47.8 — kernels of two queues do overlap (each takes 1.5 × as long) but the
         pair is no faster than the two in sequence, and every extra launch costs its boundary.  Default 1 = the single-stream schedule;
         the split stays selectable and tested (results: forward values unchanged bit for bit — row-wise kernels; each chain draws its
-        dropout masks from its own seed)."""
-        n = max(1, min(int(os.environ.get("LAKO_DEC_CHAINS", "1")), B // 2)) if B >= 4 else 1
+        dropout masks from its own seed).
+        `n` = 1 with p = 0: the whole batch as ONE chain without dropout whatever the environment says (`score`: T = its C·T rows per sample)."""
+        n = n or (max(1, min(int(os.environ.get("LAKO_DEC_CHAINS", "1")), B // 2)) if B >= 4 else 1)
         chains = []
         for c in range(n):
             b0, b1 = c * B // n, (c + 1) * B // n
@@ -872,6 +981,37 @@ class Engine:
             kv = kv[ch["kv_r"][0]:ch["kv_r"][1]]
         return self._heads(kv, ch["kv_b"], ch["kv_t"] if ch["kv_r"] is None else kv.shape[0] // ch["kv_b"], col0)
 
+    def _rel_table(self, ws, name, vec, T):
+        """the decoder-side relative-position table `vec` expanded to [H, 2T − 1] in the workspace buffer `name`"""
+        rel = self._buf(ws, name, (self.cfg.num_heads, 2 * T - 1), torch.float32)
+        self.ops.relpos_expand(vec.p, self._lut(T, T, False), rel)
+        return rel
+
+    def _dec_setup(self, ws, labels, T, Tx, bt, xa, keep=True, rel=None):
+        """The workspace of one teacher-forced decoder pass over labels [rows, T] (−100 = ignore): the shifted ids, the relative-position
+        table (`rel`: the one an earlier pass of the call built), every layer's hidden states, the final norm's output and statistics, the
+        encoder-state cross-attention's buffers for Tx query positions per sample (keep: _xattn_buffers).  → (rel, xb, dec_out)"""
+        Md, d, Ld = labels.numel(), self.cfg.d_model, self.cfg.num_decoder_layers
+        self.ops.shift_right(labels, self._buf(ws, "d.ids", tuple(labels.shape), torch.int64))
+        if rel is None:
+            rel = self._rel_table(ws, "d.rel", self.dec_rel, T)
+        xb = self._xattn_buffers(ws, bt.B, bt.N, bt.L, Tx, Ld, xa.splits, keep=keep) if xa is not None else None
+        for i in range(Ld + 1):
+            self._buf(ws, f"d.h{i}", (Md, d))
+        dec_out = self._buf(ws, "d.out", (Md, d))
+        self._buf(ws, "d.rsf", (Md,), torch.float32)
+        return rel, xb, dec_out
+
+    def _dec_norm_gemm(self, h, ln, xn, rs, w, out, **epi):
+        """xn = RMSNorm(h)·ln, rs its statistics; out = epilogue(xn · wᵀ).  The norm is formed inside the projection's kernel where the
+        library can (LAKO_EPI_NORM_A, the decoder's B·T <= 256 rows): one launch, xn and rs still written.  LAKO_DEC_FUSE_NORM=0: two."""
+        eps = self.cfg.layer_norm_epsilon
+        if os.environ.get("LAKO_DEC_FUSE_NORM", "1") != "0":
+            self.ops.gemm_nt(h, w, out, norm=(ln, eps, xn, rs), **epi)
+        else:
+            self.ops.rmsnorm_fwd(h, ln, xn, rs, eps)
+            self.ops.gemm_nt(xn, w, out, **epi)
+
     def _dec_layer_fwd(self, ws, i, ch, enc_out, kv, rel, T, S, Tx=None):
         """One decoder block (HF5:448-509) on the rows of one chain: RMSNorm → QKV → causal self-attention → O + residual → RMSNorm →
         cross-attention query → cross-attention → O + residual → RMSNorm → FFN + residual.
@@ -891,29 +1031,16 @@ class Engine:
         h = ws[f"d.h{i}"][ch["r0"]:ch["r1"]]
         if i == 0:
             ops.embed_fwd(ws["d.ids"].view(-1)[ch["r0"]:ch["r1"]], self.shared.w, h, dr(S_DEC_EMBED))
-        xn1 = R(f"d.xn1.{i}", d)
-        # (the norm in front of a projection is formed inside the projection's kernel where the library can — LAKO_EPI_NORM_A, the decoder's
-        # B·T <= 256 rows: one launch instead of two; xn / rstd are still written, the backward reads them.  LAKO_DEC_FUSE_NORM=0: two launches)
-        fuse_norm = os.environ.get("LAKO_DEC_FUSE_NORM", "1") != "0"
-        qkv = R(f"d.qkv.{i}", 3 * inner)
-        if fuse_norm:
-            ops.gemm_nt(h, lw["qkv"].w, qkv, norm=(lw["ln1"].p, eps, xn1, R(f"d.rs1.{i}", 0, torch.float32)))
-        else:
-            ops.rmsnorm_fwd(h, lw["ln1"].p, xn1, R(f"d.rs1.{i}", 0, torch.float32), eps)
-            ops.gemm_nt(xn1, lw["qkv"].w, qkv)
+        xn1, qkv = R(f"d.xn1.{i}", d), R(f"d.qkv.{i}", 3 * inner)
+        self._dec_norm_gemm(h, lw["ln1"].p, xn1, R(f"d.rs1.{i}", 0, torch.float32), lw["qkv"].w, qkv)
         c1 = R(f"d.ctx.{i}", inner)
         st = self._buf(ws, f"d.st.{i}", (Md // T, H, T, 4), torch.float32)[sb0:sb1]
         ops.attn_fwd(self._heads(qkv, Bs, T, 0), self._heads(qkv, Bs, T, inner), self._heads(qkv, Bs, T, 2 * inner),
                      self._heads(c1, Bs, T, 0), st, rel_bias=rel, rel_off=T - 1, causal=True, drop=dr(_dec_site(i, 0)))
         h1 = R(f"d.h1.{i}", d)
         ops.gemm_nt(c1, lw["o"].w, h1, resid=h, drop=dr(_dec_site(i, 1)))
-        xn2 = R(f"d.xn2.{i}", d)
-        qc = R(f"d.qc.{i}", inner)
-        if fuse_norm:
-            ops.gemm_nt(h1, lw["cq"].w, qc, norm=(lw["ln2"].p, eps, xn2, R(f"d.rs2.{i}", 0, torch.float32)))
-        else:
-            ops.rmsnorm_fwd(h1, lw["ln2"].p, xn2, R(f"d.rs2.{i}", 0, torch.float32), eps)
-            ops.gemm_nt(xn2, lw["cq"].w, qc)
+        xn2, qc = R(f"d.xn2.{i}", d), R(f"d.qc.{i}", inner)
+        self._dec_norm_gemm(h1, lw["ln2"].p, xn2, R(f"d.rs2.{i}", 0, torch.float32), lw["cq"].w, qc)
         c2 = R(f"d.cctx.{i}", inner)
         if ch["xa"] is not None:
             self._xattn_fwd(ch["xb"], ch["xa"], i, qc, enc_out, c2, Bc, Tx, S, dr(_dec_site(i, 2)))
@@ -923,15 +1050,10 @@ class Engine:
                          self._heads(c2, Bc, Tx, 0), cst, drop=dr(_dec_site(i, 2)), **ch["ckw"])
         h2 = R(f"d.h2.{i}", d)
         ops.gemm_nt(c2, lw["co"].w, h2, resid=h1, drop=dr(_dec_site(i, 3)))
-        xn3 = R(f"d.xn3.{i}", d)
-        a1 = R(f"d.a1.{i}", f)
+        xn3, a1 = R(f"d.xn3.{i}", d), R(f"d.a1.{i}", f)
         # gated: the product writes pre = [a | b] (kept for backward), then a1 = dropout(gelu_new(a) ⊙ b)
         out1, act = (R(f"d.pre.{i}", 2 * f), {}) if cfg.gated else (a1, dict(relu=True, drop=dr(_dec_site(i, 4))))
-        if fuse_norm:
-            ops.gemm_nt(h2, lw["wi"].w, out1, norm=(lw["ln3"].p, eps, xn3, R(f"d.rs3.{i}", 0, torch.float32)), **act)
-        else:
-            ops.rmsnorm_fwd(h2, lw["ln3"].p, xn3, R(f"d.rs3.{i}", 0, torch.float32), eps)
-            ops.gemm_nt(xn3, lw["wi"].w, out1, **act)
+        self._dec_norm_gemm(h2, lw["ln3"].p, xn3, R(f"d.rs3.{i}", 0, torch.float32), lw["wi"].w, out1, **act)
         if cfg.gated:
             ops.gated_gelu_fwd(out1, a1, dr(_dec_site(i, 4)))
         h_out = ws[f"d.h{i + 1}"][ch["r0"]:ch["r1"]]
@@ -1045,50 +1167,23 @@ class Engine:
         cfg, ops = self.cfg, self.ops
         B, N, L = input_ids.shape
         T = labels.shape[1]
-        d, f, inner, H, V = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads, cfg.vocab_size
+        H, V, S, Ld = cfg.num_heads, cfg.vocab_size, N * L, cfg.num_decoder_layers
         p = float(cfg.dropout_rate) if training else 0.0
         seed = (self.seed_base * 1000003 + self.step_count) & 0xFFFFFFFF
         ws = self._workspace(("train", B, N, L, T))
-        ctx = _Ctx(B=B, N=N, L=L, T=T, p=p, seed=seed, ws=ws)
-        ctx.ids = input_ids.reshape(-1).contiguous()
-        ctx.mask_u8 = attention_mask.reshape(B * N, L).to(torch.uint8).contiguous()
-        ctx.labels = labels.reshape(-1).contiguous()
-        dr = (lambda site: (p, seed, site)) if p > 0 else (lambda site: None)
-        eps = cfg.layer_norm_epsilon
-        ctx.ckpt = bool(self.use_checkpoint and training)
-        rag = ctx.rag = self._legacy_layout(self._ragged_batch(attention_mask, B, N, L, lengths), T)
-        self._row_cap = {rag.M: B * N * L} if rag is not None else {}
-        enc_ids = ctx.ids if rag is None else self._packed_ids(ws, ctx.ids, rag, L)
-        ctx.enc_ids = enc_ids
-        xa = ctx.xa = self._xattn_plan(rag, B, N, L, T * H)
-        self.xattn_active = xa is not None         # (bench.py / tests: which formulation the last forward ran)
-        ctx.enc_mask = self._enc_mask(rag, ctx.mask_u8)
-        enc_out, kv = self._encode(ws, enc_ids, ctx.enc_mask, B * N, L, p, seed, save="ckpt" if ctx.ckpt else True, rag=rag,
-                                   want_kv=xa is None)
+        ckpt = bool(self.use_checkpoint and training)
+        ctx, enc_out, kv = self._batch(ws, input_ids, attention_mask, lengths, rows_q=T * H, T=T, p=p, seed=seed, save="ckpt" if ckpt else True)
+        ctx.T, ctx.p, ctx.seed, ctx.ckpt, ctx.labels = T, p, seed, ckpt, labels.reshape(-1).contiguous()
         # ---- decoder ------------------------------------------------------------------------
-        Md, S, Ld = B * T, N * L, cfg.num_decoder_layers
-        if rag is None:      # cross-attention keys: [B, N·L] with the padding mask, or each sample's packed valid tokens
-            kb, kt, ckw = B, S, dict(key_mask=ctx.mask_u8.view(B, S))
-        else:
-            kb, kt, ckw = 1, rag.M, dict(k_off=rag.soff, max_k=S)
-        dec_ids = self._buf(ws, "d.ids", (B, T), torch.int64)
-        ops.shift_right(labels.contiguous(), dec_ids)
-        ctx.dec_ids = dec_ids
-        rel = self._buf(ws, "d.rel", (H, 2 * T - 1), torch.float32)
-        ops.relpos_expand(self.dec_rel.p, self._lut(T, T, False), rel)
+        kb, kt, ckw = self._cross_keys(ctx)
+        rel, xb, dec_out = self._dec_setup(ws, labels.contiguous(), T, T, ctx, ctx.xa)
         if self.dec_xrel is not None:      # (_legacy_layout)
-            xrel = self._buf(ws, "d.xrel", (H, 2 * T - 1), torch.float32)
-            ops.relpos_expand(self.dec_xrel.p, self._lut(T, T, False), xrel)
-            ckw = dict(ckw, rel_bias=xrel, rel_off=T - 1)
-        xb = self._xattn_buffers(ws, B, N, L, T, Ld, xa.splits) if xa is not None else None
-        for i in range(Ld + 1):
-            self._buf(ws, f"d.h{i}", (Md, d))
-        dec_out = self._buf(ws, "d.out", (Md, d))
-        self._buf(ws, "d.rsf", (Md,), torch.float32)
-        chains = ctx.chains = self._dec_chains(B, T, p, seed, xa, xb, rag, kb, kt, ckw)
+            ckw = dict(ckw, rel_bias=self._rel_table(ws, "d.xrel", self.dec_xrel, T), rel_off=T - 1)
+        ctx.cross = (kb, kt, ckw)
+        chains = ctx.chains = self._dec_chains(B, T, p, seed, ctx.xa, xb, ctx.rag, *ctx.cross)
         # (embedding → blocks → final norm per chain of samples; the LM head and the loss see all rows again)
         self._run_chains(chains, Ld, lambda i, ch: self._dec_layer_fwd(ws, i, ch, enc_out, kv, rel, T, S))
-        logits = self._buf(ws, "d.logits", (Md, V), torch.float32)
+        logits = self._buf(ws, "d.logits", (B * T, V), torch.float32)
         ops.gemm_nt(dec_out, self.lm_head.w, logits, alpha=self.head_alpha)       # tied LM head × d_model^-0.5, or the untied head
         loss_buf = self._buf(ws, "d.loss", (2,), torch.float32)
         ops.ce_fwd_bwd(logits, ctx.labels, loss_buf, None)
@@ -1116,44 +1211,26 @@ class Engine:
         if candidates.dim() != 3 or candidates.shape[0] != B or candidates.dtype != torch.int64 or candidates.numel() == 0:
             raise ValueError(f"score: candidates must be int64 [B={B}, C, T], got {tuple(candidates.shape)} {candidates.dtype}")
         C, T = int(candidates.shape[1]), int(candidates.shape[2])
-        d, H, V, Ld, S = cfg.d_model, cfg.num_heads, cfg.vocab_size, cfg.num_decoder_layers, N * L
+        H, Ld, S = cfg.num_heads, cfg.num_decoder_layers, N * L
         chunk = max(1, min(C, int(chunk) if chunk else 4096 // (B * T)))
         ws = self._workspace(("score", B, N, L, T, chunk))
-        ids = input_ids.reshape(-1).contiguous()
-        mask_u8 = attention_mask.reshape(B * N, L).to(torch.uint8).contiguous()
-        rag = self._ragged_batch(attention_mask, B, N, L, lengths)
-        self._row_cap = {rag.M: B * N * L} if rag is not None else {}
-        enc_ids = ids if rag is None else self._packed_ids(ws, ids, rag, L)
-        xa = self._xattn_plan(rag, B, N, L, chunk * T * H)
-        self.xattn_active = xa is not None
-        enc_out, kv = self._encode(ws, enc_ids, self._enc_mask(rag, mask_u8), B * N, L, 0.0, 0, save=False, rag=rag, want_kv=xa is None)
-        if rag is None:
-            kb, kt, ckw = B, S, dict(key_mask=mask_u8.view(B, S))
-        else:
-            kb, kt, ckw = 1, rag.M, dict(k_off=rag.soff, max_k=S)
-        rel = self._buf(ws, "d.rel", (H, 2 * T - 1), torch.float32)
-        ops.relpos_expand(self.dec_rel.p, self._lut(T, T, False), rel)
+        bt, enc_out, kv = self._batch(ws, input_ids, attention_mask, lengths, rows_q=chunk * T * H)
+        keys, xa = self._cross_keys(bt), bt.xa
+        rel = self._rel_table(ws, "d.rel", self.dec_rel, T)
         score = torch.empty(B, C, dtype=torch.float32, device=self.device)
         n_valid = torch.empty(B, C, dtype=torch.int32, device=self.device)
         for c0 in range(0, C, chunk):
             c = min(chunk, C - c0)
             wd = ws if c == chunk else ws.setdefault("tail", {})      # the last, smaller chunk: decoder buffers of its own shapes
-            Md, Tx = B * c * T, c * T
+            Tx = c * T
             labels = candidates[:, c0:c0 + c].reshape(B * c, T).contiguous()
-            ops.shift_right(labels, self._buf(wd, "d.ids", (B * c, T), torch.int64))
-            xb = None
-            if xa is not None:
-                if c != chunk:
-                    xa = self._xattn_plan(rag, B, N, L, Tx * H)
-                xb = self._xattn_buffers(wd, B, N, L, Tx, Ld, xa.splits, keep=False)
-            for i in range(Ld + 1):
-                self._buf(wd, f"d.h{i}", (Md, d))
-            dec_out = self._buf(wd, "d.out", (Md, d))
-            self._buf(wd, "d.rsf", (Md,), torch.float32)
-            ch = dict(c=0, b0=0, b1=B, B=B, r0=0, r1=Md, xa=xa, xb=xb, kv_b=kb, kv_t=kt, kv_r=None, ckw=ckw, dr=lambda site: None)
+            if xa is not None and c != chunk:
+                xa = self._xattn_plan(bt.rag, B, N, L, Tx * H)
+            _, xb, dec_out = self._dec_setup(wd, labels, T, Tx, bt, xa, keep=False, rel=rel)
+            ch = self._dec_chains(B, Tx, 0.0, 0, xa, xb, bt.rag, *keys, n=1)[0]
             for i in range(Ld):
                 self._dec_layer_fwd(wd, i, ch, enc_out, kv, rel, T, S, Tx=Tx)
-            logits = self._buf(wd, "d.logits", (Md, V), torch.float32)
+            logits = self._buf(wd, "d.logits", (B * Tx, cfg.vocab_size), torch.float32)
             ops.gemm_nt(dec_out, self.lm_head.w, logits, alpha=self.head_alpha)
             if c == C:
                 ops.seq_logprob(logits, labels.view(-1), score.view(-1), n_valid.view(-1), T)
@@ -1232,10 +1309,6 @@ class Engine:
         Md, Me, S, Ld, Le = B * T, (rag.M if rag is not None else B * N * L), N * L, cfg.num_decoder_layers, cfg.num_layers
         dr = (lambda site: (p, seed, site)) if p > 0 else (lambda site: None)
         tmp = self._workspace(("bwd", B, N, L, T))
-        if rag is None:
-            kb, kt, ckw = B, S, dict(key_mask=ctx.mask_u8.view(B, S))
-        else:
-            kb, kt, ckw = 1, rag.M, dict(k_off=rag.soff, max_k=S)
         # ---- loss + LM head ------------------------------------------------------------------
         dlog = self._buf(tmp, "dlogits", (Md, V))
         ops.ce_fwd_bwd(ws["d.logits"], ctx.labels, self._buf(tmp, "loss2", (2,), torch.float32), dlog, upstream)
@@ -1395,6 +1468,34 @@ class Engine:
         are those of the PROCESSED distribution (temperature applied, truncated tokens at −∞), which say how likely the sampler was to
         pick the token, not how likely the model finds the answer — the quantity a re-ranker wants is the latter."""
         K, sampled = int(num_return_sequences), bool(do_sample or return_scores)
+        self._check_generate_args(do_sample, temperature, top_k, top_p, num_return_sequences, capture_scores)
+        if self.shadows_stale:
+            self.refresh_shadows()
+        B, N, L = input_ids.shape
+        ws = self._workspace(("gen", B, N, L, max_length) + ((K, "s") if sampled else ()))
+        sparams = self._sampler_params(ws, do_sample, temperature, top_k, top_p, seed) if sampled else None
+        # cross-attention in the encoder-state space (R = H query rows per sample and step; no K/V projection of the N·L encoder
+        # states): five launches per layer and step instead of one — slower while the host's launch rate bounds the loop (eager:
+        # 113 ms against 93 ms for 50 tokens at config 2), faster once a step is one graph launch.  Never when the raw scores are
+        # captured: those come out of the projected kernel in the reference's layout.  LAKO_XATTN_GENERATE=0/1 overrides.
+        use_graph = self.device.type == "cuda" and not capture_scores and getattr(self.ops, "probe", None) is None and \
+            os.environ.get("LAKO_GEN_GRAPH", "1") != "0"
+        use_x = os.environ.get("LAKO_XATTN_GENERATE", "1" if use_graph else "0") == "1" and not capture_scores
+        # valid tokens only (as in forward_loss) unless the raw scores are captured: those are laid out per padded position
+        bt, enc_out, kv = self._batch(ws, input_ids, attention_mask, lengths, rows_q=K * self.cfg.num_heads if use_x else None, T=max_length,
+                         keep_padding=capture_scores)
+        g = _GenState(self, ws, bt, enc_out, kv, max_length, K, sampled, capture_scores, sparams)
+        n_out = self._gen_drive(g, lambda t: self._gen_step(g, t), use_graph)
+        out = g.seq[:, :n_out].clone()
+        if capture_scores:
+            # [B, H, n_layers, S] — the layout get_crossattention_scores builds with torch.cat(dim=2), src/model.py:152-160
+            cs = g.scores[:, :, :, 0, :].permute(1, 2, 0, 3).contiguous()
+            return (out, cs, g.score.view(B, K).clone()) if return_scores else (out, cs)
+        return (out, g.score.view(B, K).clone()) if return_scores else out
+
+    def _check_generate_args(self, do_sample, temperature, top_k, top_p, num_return_sequences, capture_scores):
+        """the argument errors of generate: raised before anything runs"""
+        K = int(num_return_sequences)
         if not temperature > 0:
             raise ValueError(f"temperature must be > 0, got {temperature}")
         if not 0 < top_p <= 1:
@@ -1409,205 +1510,109 @@ class Engine:
             raise ValueError("do_sample=True while the cross-attention scores are captured: the capture belongs to the greedy decode")
         if K > 1 and self.cfg.legacy_cross_bias:
             raise ValueError("num_return_sequences > 1 is not implemented with legacy_cross_bias")
-        if self.shadows_stale:
-            self.refresh_shadows()
-        cfg, ops = self.cfg, self.ops
-        B, N, L = input_ids.shape
-        d, f, inner, H, V = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads, cfg.vocab_size
-        S, Ld, eps, dk = N * L, cfg.num_decoder_layers, cfg.layer_norm_epsilon, cfg.d_kv
-        BK = B * K                     # decoder rows
-        ws = self._workspace(("gen", B, N, L, max_length) + ((K, "s") if sampled else ()))
-        if sampled:
-            # the sampler's settings live in device memory at a stable address (the kernel reads them: captured steps replay unchanged
-            # under other settings); the step index is an argument baked into each step's graph, as `pos` is
-            if seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # torch's global (host) generator
-            seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-            words = np.array([np.float32(temperature).view(np.uint32), np.float32(top_p).view(np.uint32),
-                              (min(int(top_k), 0x7FFFFFFF) if do_sample else 1), seed & 0xFFFFFFFF, seed >> 32, 0, 0, 0], dtype=np.uint32)
-            sparams = self._buf(ws, "g.sparams", (8,), torch.int32)
-            if "g.sparams_host" not in ws:       # pinned: the upload is an enqueue like every other launch of the call
-                ws["g.sparams_host"] = torch.zeros(8, dtype=torch.int32).pin_memory() if torch.cuda.is_available() else \
-                    torch.zeros(8, dtype=torch.int32)
-            ws["g.sparams_host"].copy_(torch.from_numpy(words.view(np.int32)))      # (the last call ended with a wait on its last step)
-            sparams.copy_(ws["g.sparams_host"], non_blocking=True)
-        ids = input_ids.reshape(-1).contiguous()
-        mask_u8 = attention_mask.reshape(B * N, L).to(torch.uint8).contiguous()
-        # valid tokens only (as in forward_loss) unless the raw scores are captured: those are laid out per padded position
-        rag = None if capture_scores else self._legacy_layout(self._ragged_batch(attention_mask, B, N, L, lengths), max_length)
-        if capture_scores:
-            self._all_valid = False      # (_ragged_batch did not look at this mask: nothing is known about its padding — _enc_mask keeps it)
-        self._row_cap = {rag.M: B * N * L} if rag is not None else {}
-        # what changes from call to call is COPIED into workspace buffers (stable addresses: the decode steps below are captured
-        # into HIP graphs): the samples' key offsets of the unpadded batch, or the key mask of the padded one
-        if rag is None:
-            kmask = self._buf(ws, "g.kmask", (B, S), torch.uint8)
-            kmask.copy_(mask_u8.view(B, S))
-            kb, kt, ckw, mode = B, S, dict(key_mask=kmask), "p"
-        else:
-            koff = self._buf(ws, "g.koff", (B + 1,), torch.int32)
-            koff.copy_(rag.soff)
-            ids, kb, kt, ckw, mode = self._packed_ids(ws, ids, rag, L), 1, rag.M, dict(k_off=koff, max_k=S), "r"
-        # cross-attention in the encoder-state space (R = H query rows per sample and step; no K/V projection of the N·L encoder
-        # states): five launches per layer and step instead of one — slower while the host's launch rate bounds the loop (eager:
-        # 113 ms against 93 ms for 50 tokens at config 2), faster once a step is one graph launch.  Never when the raw scores are
-        # captured: those come out of the projected kernel in the reference's layout.  LAKO_XATTN_GENERATE=0/1 overrides.
-        use_graph = self.device.type == "cuda" and not capture_scores and getattr(ops, "probe", None) is None and \
-            os.environ.get("LAKO_GEN_GRAPH", "1") != "0"
-        use_x = os.environ.get("LAKO_XATTN_GENERATE", "1" if use_graph else "0") == "1" and not capture_scores
-        xa = self._xattn_plan(rag, B, N, L, K * H) if use_x else None
-        self.xattn_active = xa is not None
-        enc_out, kv = self._encode(ws, ids, self._enc_mask(rag, mask_u8), B * N, L, 0.0, 0, save=False, rag=rag, want_kv=xa is None)
-        if xa is not None:
-            # (the K sequences of a question: K·H query rows of its sample — the unfused kernels take any row count, the one-pass
-            # kernel carries them as 16-row tiles, several per workgroup: lako_xattn_decode_multi)
-            mode += "x"
-            cap = B * (-(-S // 256) * 256)
-            xoff = self._buf(ws, "g.xoff", (2, B + 1), torch.int32)
-            xoff[0].copy_(xa.k_off)
-            xoff[1].copy_(xa.p_off)
-            xq = self._buf(ws, "g.xq", (B, K * H, d))
-            xs = self._buf(ws, "g.xs", (K * H, cap), torch.float32)      # launched over all `cap` columns: tiles past the batch's
-            xp = self._buf(ws, "g.xp", (K * H, cap))                      # last key column exit at once
-            xst = self._buf(ws, "g.xst", (B, K * H, 2), torch.float32)
-            xc = self._buf(ws, "g.xc", (xa.splits, B, K * H, d), torch.float32)
-            # scores, softmax and context of a decode step in one pass over the encoder states when the shapes allow
-            # (K > 1: only up to XDM_MAX_K sequences per question — above, the unfused kernels' K·H-row MFMA tiles beat the one-pass
-            # kernel's row tiles although they read E twice: DESIGN.md §3 "Sampled decoding"; LAKO_XATTN_DECODE=1 forces the one pass)
-            xd = os.environ.get("LAKO_XATTN_DECODE")
-            fused = dk == 64 and getattr(ops, "xattn_decode_ok", lambda *_: False)(H, d) and xd != "0" and (K <= XDM_MAX_K or xd == "1")
-            if fused:
-                # (≈256 workgroups: a workgroup carries as many of a question's sequences as the library's plan gives it row tiles)
-                tiles = getattr(ops, "xattn_decode_multi_tiles", lambda d_, k_: min(4, k_))(d, K)
-                zd = max(1, min(64, 256 // (B * -(-K // tiles))))
-                pml = self._buf(ws, "g.xpml", (zd, BK, 16, 2), torch.float32)
-                pc = self._buf(ws, "g.xpc", (zd, BK, 16, d), torch.float32)
-                mode += "f"
-        if sampled:
-            mode += f"s{K}"
-        ML = max_length
-        seq = self._buf(ws, "g.seq", (BK, ML), torch.int64)
-        nxt = self._buf(ws, "g.next", (BK,), torch.int64)
-        done = self._buf(ws, "g.done", (BK,), torch.uint8)
-        score = self._buf(ws, "g.score", (BK,), torch.float32) if sampled else None
-        # finished-row count after every step, mirrored to pinned host memory: the host looks at the count of step t − LAG
-        # (an event wait on that step only), so it keeps enqueueing LAG steps ahead of the GPU instead of draining the queue
-        # after every token; the LAG extra steps a finished batch may run emit pad for every row and are cut off below
-        ndone = self._buf(ws, "g.ndone", (ML,), torch.int32)
-        if "g.ndone_host" not in ws or ws["g.ndone_host"].numel() < ML:
-            ws["g.ndone_host"] = torch.zeros(ML, dtype=torch.int32).pin_memory() if torch.cuda.is_available() else \
-                torch.zeros(ML, dtype=torch.int32)
-        ndone_host, LAG, events = ws["g.ndone_host"], 2, []
-        for t_ in (seq, nxt, done, ndone) + ((score,) if sampled else ()):
-            ops.zero_(t_)                                  # decoder_start_token_id = pad = 0
-        rel = self._buf(ws, "g.rel", (H, 2 * ML - 1), torch.float32)
-        ops.relpos_expand(self.dec_rel.p, self._lut(ML, ML, False), rel)
-        xrel = None
-        if self.dec_xrel is not None:
-            # legacy_cross_bias (_legacy_layout).  Step t's query sits at position t: table index key − t + ML − 1.  With score capture the
-            # reference runs ITS cross-attention forward (src/model.py:286-349), which sizes the bias by the step's own query length —
-            # 1 under the key / value cache — so every step sees the bias of position 0: one constant per head (src/model.py:323-325)
-            xrel = self._buf(ws, "g.xrel", (H, 2 * ML - 1), torch.float32)
-            ops.relpos_expand(self.dec_xrel.p, self._lut(ML, ML, False), xrel)
-        # per layer [B, max_length, (q | k | v)]: ONE projection GEMM per step writes the step's q, k and v into row t; q is read
-        # back from there, k and v stay as the cache
-        cache = [self._buf(ws, f"g.cache.{i}", (BK, ML, 3 * inner)) for i in range(Ld)]
-        scores = self._buf(ws, "g.scores", (Ld, B, H, 1, S), torch.float32) if capture_scores else None
-        h, h1, h2, xn = (self._buf(ws, f"g.{n}", (BK, d)) for n in ("h", "h1", "h2", "xn"))
-        rs = self._buf(ws, "g.rs", (BK,), torch.float32)
-        c1, qc, c2 = (self._buf(ws, f"g.{n}", (BK, inner)) for n in ("c1", "qc", "c2"))
-        st = self._buf(ws, "g.st", (BK, H, 1, 4), torch.float32)
-        stx = self._buf(ws, "g.stx", (B, H, K, 4), torch.float32) if K > 1 else st      # the cross-attention's: K query positions per sample
-        a1 = self._buf(ws, "g.a1", (BK, f))
-        pre = self._buf(ws, "g.pre", (BK, 2 * f)) if cfg.gated else None
-        logits = self._buf(ws, "g.logits", (BK, V), torch.float32)
-        def step(t):
-            """enqueue decode step t (reads nxt, writes seq[:, t + 1], nxt, done, ndone[t])"""
-            ops.embed_fwd(nxt, self.shared.w, h)
-            fz = os.environ.get("LAKO_DEC_FUSE_NORM", "1") != "0"      # the norm inside the projection's kernel (LAKO_EPI_NORM_A), as in training
-            nrm = (lambda w_: dict(norm=(w_, eps, xn, rs))) if fz else None
-            xkw = ckw if xrel is None else dict(ckw, rel_bias=xrel, rel_off=ML - 1 - (0 if capture_scores else t))
-            for i in range(Ld):
-                lw = self.dec[i]
-                if fz:
-                    ops.gemm_nt(h, lw["qkv"].w, cache[i].view(BK, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner], **nrm(lw["ln1"].p))
-                else:
-                    ops.rmsnorm_fwd(h, lw["ln1"].p, xn, rs, eps)
-                    ops.gemm_nt(xn, lw["qkv"].w, cache[i].view(BK, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner])
-                qs = cache[i][:, t:t + 1, :inner].unflatten(2, (H, dk))
-                kc = cache[i][:, :t + 1, inner:2 * inner].unflatten(2, (H, dk))
-                vc = cache[i][:, :t + 1, 2 * inner:].unflatten(2, (H, dk))
-                ops.attn_fwd(qs, kc, vc, c1.view(BK, 1, H, dk), st, rel_bias=rel, rel_off=ML - 1 - t)
-                ops.gemm_nt(c1, lw["o"].w, h1, resid=h)
-                if fz:
-                    ops.gemm_nt(h1, lw["cq"].w, qc, **nrm(lw["ln2"].p))
-                else:
-                    ops.rmsnorm_fwd(h1, lw["ln2"].p, xn, rs, eps)
-                    ops.gemm_nt(xn, lw["cq"].w, qc)
-                if xa is None:
-                    ops.attn_fwd(qc.view(B, K, H, dk), self._heads(kv, kb, kt, 2 * i * inner),
-                                 self._heads(kv, kb, kt, (2 * i + 1) * inner), c2.view(B, K, H, dk), stx,
-                                 scores_out=scores[i] if (capture_scores and t == 0) else None, **xkw)
-                else:
-                    ops.headbatch_nt(qc.view(B, K, H, dk), self._xw(i, "k", transposed=True), xq.view(B, K, H, d))
-                    if fused:
-                        if K == 1:
-                            ops.xattn_decode(xq, enc_out, xoff[0], pml, pc)
-                        else:
-                            ops.xattn_decode_multi(xq.view(B, K, H, d), enc_out, xoff[0], pml, pc)
-                        r0 = (2 * i + 1) * inner
-                        ops.xattn_decode_combine(pml, pc, self.kv_all.w[r0:r0 + inner], c2, H)
-                    else:
-                        ops.xattn_scores(xq, enc_out, xoff[0], xoff[1], cap, xs)
-                        ops.xattn_softmax_fwd(xs, xst, xp, xoff[0], xoff[1], K, H, S)
-                        ops.xattn_context(xp, enc_out, xoff[0], xoff[1], xc)
-                        ops.headbatch_nt(xc.view(xa.splits, B, K, H, d), self._xw(i, "v"), c2.view(B, K, H, dk))
-                ops.gemm_nt(c2, lw["co"].w, h2, resid=h1)
-                out1, act = (pre, {}) if cfg.gated else (a1, dict(relu=True))
-                if fz:
-                    ops.gemm_nt(h2, lw["wi"].w, out1, **nrm(lw["ln3"].p), **act)
-                else:
-                    ops.rmsnorm_fwd(h2, lw["ln3"].p, xn, rs, eps)
-                    ops.gemm_nt(xn, lw["wi"].w, out1, **act)
-                if cfg.gated:
-                    ops.gated_gelu_fwd(pre, a1, None)
-                ops.gemm_nt(a1, lw["wo"].w, h, resid=h2)
-            ops.rmsnorm_fwd(h, self.dec_final.p, xn, rs, eps)
-            ops.gemm_nt(xn, self.lm_head.w, logits, alpha=self.head_alpha)
-            if sampled:
-                ops.sample_step(logits, seq, t + 1, nxt, done, score, ndone[t:t + 1], sparams, t, K, cfg.eos_token_id, cfg.pad_token_id)
-            else:
-                ops.greedy_step(logits, seq, t + 1, nxt, done, ndone[t:t + 1], cfg.eos_token_id, cfg.pad_token_id)
 
-        # A decode step is ≈130 dependent launches of a few µs each: the host's launch rate bounds the loop.  After one eager call
-        # per (shape, mode) — the kernels' one-time setup must not happen under capture — every step position is captured ONCE into a
-        # HIP graph (kernel arguments that depend on t are baked in; everything that changes from call to call lives in workspace
-        # buffers whose addresses do not: the offsets / key mask are COPIED into them above) and replayed: one launch per token.
+    def _sampler_params(self, ws, do_sample, temperature, top_k, top_p, seed):
+        """The sampler's settings live in device memory at a stable address (the kernel reads them: captured steps replay unchanged
+        under other settings); the step index is an argument baked into each step's graph, as `pos` is.  → int32 [8] `g.sparams`"""
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # torch's global (host) generator
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        words = np.array([np.float32(temperature).view(np.uint32), np.float32(top_p).view(np.uint32),
+                          (min(int(top_k), 0x7FFFFFFF) if do_sample else 1), seed & 0xFFFFFFFF, seed >> 32, 0, 0, 0], dtype=np.uint32)
+        sparams = self._buf(ws, "g.sparams", (8,), torch.int32)
+        if "g.sparams_host" not in ws:       # pinned: the upload is an enqueue like every other launch of the call
+            ws["g.sparams_host"] = torch.zeros(8, dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        ws["g.sparams_host"].copy_(torch.from_numpy(words.view(np.int32)))      # (the last call ended with a wait on its last step)
+        sparams.copy_(ws["g.sparams_host"], non_blocking=True)
+        return sparams
+
+    def _gen_step(self, g, t):
+        """enqueue decode step t (reads nxt, writes seq[:, t + 1], nxt, done, ndone[t]): a decoder block per layer over the key / value
+        cache (not _dec_layer_fwd: other buffer lifetimes, other kernels), final norm, LM head, the greedy or sampling kernel"""
+        ops, cfg = self.ops, self.cfg
+        inner, H, dk = cfg.inner_dim, cfg.num_heads, cfg.d_kv
+        BK, ML, h, h1, h2, xn, rs, c1, qc, c2, a1 = g.BK, g.ML, g.h, g.h1, g.h2, g.xn, g.rs, g.c1, g.qc, g.c2, g.a1
+        ops.embed_fwd(g.nxt, self.shared.w, h)
+        xkw = g.keys[2] if g.xrel is None else dict(g.keys[2], rel_bias=g.xrel, rel_off=ML - 1 - (0 if g.capture else t))
+        for i, lw in enumerate(self.dec):
+            cache = g.cache[i]
+            self._dec_norm_gemm(h, lw["ln1"].p, xn, rs, lw["qkv"].w, cache.view(BK, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner])
+            qs = cache[:, t:t + 1, :inner].unflatten(2, (H, dk))
+            kc = cache[:, :t + 1, inner:2 * inner].unflatten(2, (H, dk))
+            vc = cache[:, :t + 1, 2 * inner:].unflatten(2, (H, dk))
+            ops.attn_fwd(qs, kc, vc, c1.view(BK, 1, H, dk), g.st, rel_bias=g.rel, rel_off=ML - 1 - t)
+            ops.gemm_nt(c1, lw["o"].w, h1, resid=h)
+            self._dec_norm_gemm(h1, lw["ln2"].p, xn, rs, lw["cq"].w, qc)
+            self._gen_cross(g, i, t, xkw)
+            ops.gemm_nt(c2, lw["co"].w, h2, resid=h1)
+            out1, act = (g.pre, {}) if cfg.gated else (a1, dict(relu=True))
+            self._dec_norm_gemm(h2, lw["ln3"].p, xn, rs, lw["wi"].w, out1, **act)
+            if cfg.gated:
+                ops.gated_gelu_fwd(g.pre, a1, None)
+            ops.gemm_nt(a1, lw["wo"].w, h, resid=h2)
+        ops.rmsnorm_fwd(h, self.dec_final.p, xn, rs, cfg.layer_norm_epsilon)
+        ops.gemm_nt(xn, self.lm_head.w, g.logits, alpha=self.head_alpha)
+        if g.sampled:
+            ops.sample_step(g.logits, g.seq, t + 1, g.nxt, g.done, g.score, g.ndone[t:t + 1], g.sparams, t, g.K, cfg.eos_token_id,
+                            cfg.pad_token_id)
+        else:
+            ops.greedy_step(g.logits, g.seq, t + 1, g.nxt, g.done, g.ndone[t:t + 1], cfg.eos_token_id, cfg.pad_token_id)
+
+    def _gen_cross(self, g, i, t, xkw):
+        """cross-attention of decode step t in layer i, qc → c2, by the call's route: on the projected K / V (`xkw`: the key arguments),
+        or on the encoder states — the unfused kernels, or scores, softmax and context in one pass (g.fused)"""
+        ops, cfg = self.ops, self.cfg
+        inner, H, dk, d, B, K, qc, c2 = cfg.inner_dim, cfg.num_heads, cfg.d_kv, cfg.d_model, g.B, g.K, g.qc, g.c2
+        if g.xa is None:
+            ops.attn_fwd(qc.view(B, K, H, dk), self._heads(g.kv, *g.keys[:2], 2 * i * inner),
+                         self._heads(g.kv, *g.keys[:2], (2 * i + 1) * inner), c2.view(B, K, H, dk), g.stx,
+                         scores_out=g.scores[i] if (g.capture and t == 0) else None, **xkw)
+            return
+        xq, xoff = g.xq, g.xoff
+        ops.headbatch_nt(qc.view(B, K, H, dk), self._xw(i, "k", transposed=True), xq.view(B, K, H, d))
+        if g.fused:
+            if K == 1:
+                ops.xattn_decode(xq, g.enc_out, xoff[0], g.pml, g.pc)
+            else:
+                ops.xattn_decode_multi(xq.view(B, K, H, d), g.enc_out, xoff[0], g.pml, g.pc)
+            r0 = (2 * i + 1) * inner
+            ops.xattn_decode_combine(g.pml, g.pc, self.kv_all.w[r0:r0 + inner], c2, H)
+        else:
+            ops.xattn_scores(xq, g.enc_out, xoff[0], xoff[1], g.cap, g.xs)
+            ops.xattn_softmax_fwd(g.xs, g.xst, g.xp, xoff[0], xoff[1], K, H, g.S)
+            ops.xattn_context(g.xp, g.enc_out, xoff[0], xoff[1], g.xc)
+            ops.headbatch_nt(g.xc.view(g.xa.splits, B, K, H, d), self._xw(i, "v"), c2.view(B, K, H, dk))
+
+    def _gen_drive(self, g, step, use_graph):
+        """Run step(t), t = 0 …, until every row has ended → the number of token columns to return.  A decode step is ≈130 dependent
+        launches of a few µs each: the host's launch rate bounds the loop.  After one eager call per (shape, mode) — the kernels' one-time
+        setup must not happen under capture — every step position is captured ONCE into a HIP graph (kernel arguments that depend on t
+        are baked in; what changes from call to call lives in workspace buffers whose addresses do not: _GenState COPIES the offsets /
+        key mask into them) and replayed: one launch per token.  `step` is the caller's: another decoding strategy brings its own."""
+        ws, ML, BK, ndone, ndone_host, LAG, events = g.ws, g.ML, g.BK, g.ndone, g.ndone_host, 2, []
         graphs = None
         if use_graph:
-            gs = ws.setdefault("g.graphs", {}).get(mode)
+            gs = ws.setdefault("g.graphs", {}).get(g.mode)
             ptrs = {k_: v.data_ptr() for k_, v in ws.items() if k_.startswith("^")}
             if gs is None or any(ptrs.get(k_) != p_ for k_, p_ in gs["ptrs"].items()):      # a workspace buffer moved: start over
-                gs = ws["g.graphs"][mode] = dict(ptrs=ptrs, warm=False, steps={}, pool=None)
+                gs = ws["g.graphs"][g.mode] = dict(ptrs=ptrs, warm=False, steps={}, pool=None)
             if gs["warm"]:
                 graphs = gs
             gs["warm"] = True
-        n_out = 1
         for t in range(ML - 1):
             if graphs is None:
                 step(t)
             else:
-                g = graphs["steps"].get(t)
-                if g is None:
-                    g = torch.cuda.CUDAGraph()
+                gr = graphs["steps"].get(t)
+                if gr is None:
+                    gr = torch.cuda.CUDAGraph()
                     if graphs["pool"] is None:
                         graphs["pool"] = torch.cuda.graph_pool_handle()
                     # thread_local: a data-loader / pin-memory thread may touch the runtime while this thread captures
-                    with torch.cuda.graph(g, pool=graphs["pool"], capture_error_mode="thread_local"):
+                    with torch.cuda.graph(gr, pool=graphs["pool"], capture_error_mode="thread_local"):
                         step(t)
-                    graphs["steps"][t] = g
-                g.replay()
-            n_out = t + 2
+                    graphs["steps"][t] = gr
+                gr.replay()
             ndone_host[t:t + 1].copy_(ndone[t:t + 1], non_blocking=True)
             if ndone.is_cuda:
                 events.append(torch.cuda.Event())
@@ -1618,11 +1623,5 @@ class Engine:
                     events[look].synchronize()
                 first = next((u for u in range(max(look - LAG, 0), look + 1) if int(ndone_host[u]) == BK), None)
                 if first is not None:        # HF stops right after the step in which the last row emitted EOS
-                    n_out = first + 2
-                    break
-        out = seq[:, :n_out].clone()
-        if capture_scores:
-            # [B, H, n_layers, S] — the layout get_crossattention_scores builds with torch.cat(dim=2), src/model.py:152-160
-            cs = scores[:, :, :, 0, :].permute(1, 2, 0, 3).contiguous()
-            return (out, cs, score.view(B, K).clone()) if return_scores else (out, cs)
-        return (out, score.view(B, K).clone()) if return_scores else out
+                    return first + 2
+        return max(ML, 1)

@@ -144,7 +144,7 @@ def unpack_params(params):
 
 
 def pack_params(temperature, top_p, top_k, seed):
-    """the 8-word buffer lako_sample_step reads (int32 view; the engine builds the same in Engine.generate)"""
+    """the 8-word buffer lako_sample_step reads (int32 view; the engine builds the same in Engine._sampler_params)"""
     seed &= 0xFFFFFFFFFFFFFFFF
     wds = np.array([np.float32(temperature).view(np.uint32), np.float32(top_p).view(np.uint32), min(top_k, 0x7FFFFFFF), seed & M32, seed >> 32,
                     0, 0, 0], dtype=np.uint32)

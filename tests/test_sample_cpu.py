@@ -172,6 +172,39 @@ def test_a_default_generate_issues_the_ops_it_issued_before_sampling_existed():
         assert all(len(k) == 5 for k in model._engine._ws_cache if k[0] == "gen")      # the workspace key of before
 
 
+def engine_call_ops():
+    """{call: op names} of a training step with dropout, a sampled generate with K = 3 and scores, and a chunked score on tiny_a"""
+    ops = _Log(RefOpsSample())
+    z, model, ids, mask = build("tiny_a", ops=ops)
+    model.config.dropout_rate = 0.1
+    got = {}
+    ops.names.clear()
+    model.train()
+    model(input_ids=ids, attention_mask=mask, labels=torch.from_numpy(z["labels"]))[0].backward()
+    model.eval()
+    got["forward_backward"] = list(ops.names)
+    ops.names.clear()
+    model.generate(ids, mask, 6, do_sample=True, top_k=3, num_return_sequences=3, seed=7, return_scores=True)
+    got["generate_sampled"] = list(ops.names)
+    ops.names.clear()
+    cand = torch.randint(2, model.config.vocab_size, (ids.shape[0], 3, 4), generator=torch.Generator().manual_seed(29))
+    cand[:, 1, 3:] = -100
+    model.score(ids, mask, cand, candidate_chunk=2)      # a full chunk and the smaller tail chunk
+    got["score"] = list(ops.names)
+    return got
+
+
+def test_the_engines_public_calls_issue_the_ops_they_issued_before_the_engine_was_cut_into_parts():
+    """tests/golden/engine_ops.json: the op names of engine_call_ops() recorded with this very proxy on the commit before
+    forward_loss / score / generate came to share their batch prologue, decoder set-up and norm + projection helper"""
+    with open(os.path.join(GOLDEN, "engine_ops.json")) as fh:
+        want = json.load(fh)
+    got = engine_call_ops()
+    assert sorted(got) == sorted(want)
+    for call, names in got.items():
+        assert names == want[call], call
+
+
 def test_the_restatement_follows_the_definition_on_a_hand_made_row():
     x = torch.tensor([0.0, 2.0, 2.0, -float("inf"), 1.0, float("nan")])
     # top_k = 1: the first of the two maxima, whatever the draw
