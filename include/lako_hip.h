@@ -607,6 +607,46 @@ int lako_sample_step(const float* logits, int64_t V, int rows, int group, int64_
                      uint8_t* done, float* score, int32_t* n_done, const void* params, int step, int64_t eos_id, int64_t pad_id,
                      lako_stream_t stream);
 
+/* ---- beam search (generate with num_beams = K > 1; csrc/beam.hip).  The semantics of transformers 5.15 `_beam_search`: per question
+ * K running beams (tokens, run[k] = fp32 sum of log-probabilities, sorted best first; before step 0 run = [0, -1e9, ...], so that step
+ * 0 expands beam 0 only), K finished slots (tokens, normalised score, raw sum, length, filled flag; sorted best first, unfilled last)
+ * and a flag open[b].  A decode step that writes token column pos (n = pos tokens generated after it) ends with the three launches
+ * below.  Two deliberate differences from HF: the columns behind a hypothesis' EOS hold pad_id (HF 5.15 fills with EOS where pad_id
+ * is 0), and callers report the RAW sum of log-probabilities (fin_raw), from which HF's ranking value raw / len^length_penalty follows.
+ * None allocates or synchronises: all may be captured into a graph.  The same inputs give the same bits on every launch.
+ *
+ * lako_beam_rows: for each of `rows` rows of fp32 logits [rows, V] (a NaN counts as -inf), with m = max x and, in a fixed summation
+ * order, lp(v) = (x_v - m) - log(sum exp(x - m)) (what lako_sample_step adds to its score; -inf where x_v = -inf): the row's n_cand
+ * best entries in the order (x descending, index ascending), written sorted as cand_acc[r][j] = run[r] + lp, cand_tok[r][j] = index.
+ * 1 <= n_cand <= min(32, V).  (A question's best 2K candidates hold at most 2K of any one row: n_cand = 2K loses nothing.) */
+int lako_beam_rows(const float* logits, int64_t V, int rows, int n_cand, const float* run, float* cand_acc, int32_t* cand_tok,
+                   lako_stream_t stream);
+/* lako_beam_merge: per question b, over cand_acc / cand_tok [B*K, 2K] (a NaN acc counts as -inf):
+ *   1. take the 2K best candidates, by acc descending, ties by the flat index k*V + token ascending (torch.topk leaves ties open: this
+ *      rule is ours).  A candidate ENDS if token == eos_id or `last` is set (the step that writes column max_length - 1).
+ *   2. the next running beams are the first K candidates that do not end, in order: run, next_ids, parent (int32: the ROW b*K + k the
+ *      beam descends from) and the token rows seq_dst[b*K + j][0 .. pos] = seq_src[parent][0 .. pos - 1] ++ token.
+ *   3. an ending candidate among the first K of the 2K is OFFERED with score acc / pos^length_penalty, unless open[b] is 0, or
+ *      early_stopping is set and all K slots were filled before the step.  The finished set becomes the best K of (old + offers), old
+ *      before new on ties: fin_score, fin_raw (= acc), fin_len (= pos + 1 columns, the start token included), fin_filled, and whole
+ *      token rows fin_dst (pad_id behind column pos), kept rows copied from fin_src.
+ *   4. open[b] &= !(all K slots filled && run[0] / pos^length_penalty <= the smallest fin_score), with the new run[0].
+ *   5. n_done[0] += K if the question is done: open[b] == 0, or early_stopping and all K slots filled, or `last`.  The caller zeroes
+ *      n_done[0] before the step: it is B*K afterwards exactly when decoding has ended.  (Closed questions keep stepping, as in HF.)
+ * seq_src / seq_dst and fin_src / fin_dst are distinct buffers [B*K, seq_ld] (int64): rows are never permuted in place.  params:
+ * DEVICE memory, 8 32-bit words read by the kernel: [0] length_penalty (float), [1] early_stopping (0 / 1), [2..7] reserved.
+ * 1 <= K <= 16, 1 <= pos < seq_ld. */
+int lako_beam_merge(const float* cand_acc, const int32_t* cand_tok, int B, int K, const int64_t* seq_src, int64_t* seq_dst,
+                    const int64_t* fin_src, int64_t* fin_dst, int64_t seq_ld, int pos, int last, float* run, int64_t* next_ids,
+                    int32_t* parent, float* fin_score, float* fin_raw, int32_t* fin_len, uint8_t* fin_filled, uint8_t* open,
+                    int32_t* n_done, const void* params, int64_t eos_id, int64_t pad_id, lako_stream_t stream);
+/* lako_beam_gather: the self-attention cache of all layers reordered by parent beam, in one launch of 16-byte loads and stores:
+ * dst[l][r][p][off .. off + width) = src[l][parent[r]][p][off .. off + width) for l < layers, r < rows, p < n_pos; all strides and
+ * sizes in bytes and multiples of 16, src != dst.  Positions >= n_pos and bytes outside [off, off + width) are neither read nor
+ * written; a row whose parent is not in [0, rows) is left alone. */
+int lako_beam_gather(const void* src, void* dst, const int32_t* parent, int layers, int rows, int n_pos, int64_t layer_bytes,
+                     int64_t row_bytes, int64_t pos_bytes, int64_t off_bytes, int64_t width_bytes, lako_stream_t stream);
+
 /* ---- per-fact aggregation of the captured step-0 cross-attention scores (src/model.py:100-115,143-204,
  * FiDT5.get_crossattention_scores; replaces its per-sample Python loops) ----------------------------------------------------
  * scores fp32 [B, H, n_layers, N·L] (raw pre-softmax scores as lako_attn_fwd's scores_out lays them out per layer),

@@ -209,6 +209,9 @@ SIGNATURES = {
     "lako_pack_ids": [vp, vp, vp, i32, i32, vp],
     "lako_greedy_step": [vp, i64, i32, vp, i64, i32, vp, vp, vp, i64, i64, vp],
     "lako_sample_step": [vp, i64, i32, i32, vp, i64, i32, vp, vp, vp, vp, vp, i32, i64, i64, vp],
+    "lako_beam_rows": [vp, i64, i32, i32, vp, vp, vp, vp],
+    "lako_beam_merge": [vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp],
+    "lako_beam_gather": [vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, i64, vp],
     "lako_fact_scores": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "lako_topk": [vp, i64, i64, i64, i32, vp, vp, vp],
     "lako_pq_assign": [vp, i64, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp],

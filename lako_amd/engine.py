@@ -168,13 +168,14 @@ class _GenState:
     BK decoder rows, ML = max_length, keys = the cross-attention's key descriptor over the stable copies.  Building it enqueues the
     zeroing of the token state and the expansion of the position tables.  Read by Engine._gen_step / _gen_cross / _gen_drive."""
 
-    def __init__(self, eng, ws, bt, enc_out, kv, ML, K, sampled, capture, sparams):
+    def __init__(self, eng, ws, bt, enc_out, kv, ML, K, sampled, capture, sparams, bparams=None):
         cfg, ops = eng.cfg, eng.ops
         d, f, inner, H, V, Ld, dk = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads, cfg.vocab_size, cfg.num_decoder_layers, cfg.d_kv
         B, S, BK, xa = bt.B, bt.N * bt.L, bt.B * K, bt.xa
         buf = lambda name, shape, dtype=None: eng._buf(ws, "g." + name, shape, dtype)       # noqa: E731
         self.ws, self.B, self.K, self.BK, self.ML, self.S, self.sampled, self.capture = ws, B, K, BK, ML, S, sampled, capture
         self.sparams, self.enc_out, self.kv, self.xa, self.fused = sparams, enc_out, kv, xa, False
+        self.bparams, self.beam = bparams, bparams is not None
         # what changes from call to call is COPIED into workspace buffers (stable addresses: the decode steps are captured into HIP
         # graphs): the samples' key offsets of the unpadded batch, or the key mask of the padded one
         if bt.rag is None:
@@ -210,6 +211,8 @@ class _GenState:
                 self.mode += "f"
         if sampled:
             self.mode += f"s{K}"
+        if self.beam:
+            self.mode += f"b{K}"
         self.seq, self.nxt, self.done = buf("seq", (BK, ML), torch.int64), buf("next", (BK,), torch.int64), buf("done", (BK,), torch.uint8)
         self.score = buf("score", (BK,), torch.float32) if sampled else None
         # finished-row count after every step, mirrored to pinned host memory: the host looks at the count of step t − LAG
@@ -228,7 +231,14 @@ class _GenState:
         self.xrel = eng._rel_table(ws, "g.xrel", eng.dec_xrel, ML) if eng.dec_xrel is not None else None
         # per layer [B, max_length, (q | k | v)]: ONE projection GEMM per step writes the step's q, k and v into row t; q is read
         # back from there, k and v stay as the cache
-        self.cache = [buf(f"cache.{i}", (BK, ML, 3 * inner)) for i in range(Ld)]
+        if self.beam:
+            # beam search: TWO cache sets in one allocation — step t runs on set t & 1 and lako_beam_gather writes the rows, reordered by
+            # parent beam, into the other one (one launch for all layers; never in place)
+            self.bcache = buf("bcache", (2, Ld, BK, ML, 3 * inner))
+            self.cache2 = [[self.bcache[s_, i] for i in range(Ld)] for s_ in range(2)]
+            self.cache = self.cache2[0]
+        else:
+            self.cache = [buf(f"cache.{i}", (BK, ML, 3 * inner)) for i in range(Ld)]
         self.scores = buf("scores", (Ld, B, H, 1, S), torch.float32) if capture else None
         self.h, self.h1, self.h2, self.xn = (buf(n, (BK, d)) for n in ("h", "h1", "h2", "xn"))
         self.c1, self.qc, self.c2 = (buf(n, (BK, inner)) for n in ("c1", "qc", "c2"))
@@ -236,6 +246,21 @@ class _GenState:
         self.stx = buf("stx", (B, H, K, 4), torch.float32) if K > 1 else self.st      # the cross-attention's: K query positions per sample
         self.a1, self.pre = buf("a1", (BK, f)), (buf("pre", (BK, 2 * f)) if cfg.gated else None)
         self.logits = buf("logits", (BK, V), torch.float32)
+        if self.beam:
+            # the beams' state (after the buffers every mode has).  Token rows of the running beams (seq2) and of the finished set (fin2)
+            # alternate between two sets like the cache: step t reads set t & 1 and writes the other.  run: Σ log-probability of the
+            # running beams, best first — [0, −1e9, …] to begin with, so that step 0 expands beam 0 only (HF's initial scores)
+            self.seq2, self.fin2 = buf("bseq", (2, BK, ML), torch.int64), buf("bfin", (2, BK, ML), torch.int64)
+            self.run, self.parent = buf("brun", (BK,), torch.float32), buf("bparent", (BK,), torch.int32)
+            self.cand_acc, self.cand_tok = buf("bcacc", (BK, 2 * K), torch.float32), buf("bctok", (BK, 2 * K), torch.int32)
+            self.fin_score, self.fin_raw = buf("bfscore", (BK,), torch.float32), buf("bfraw", (BK,), torch.float32)
+            self.fin_len, self.fin_filled = buf("bflen", (BK,), torch.int32), buf("bffilled", (BK,), torch.uint8)
+            self.open = buf("bopen", (B,), torch.uint8)
+            for t_ in (self.seq2, self.fin2, self.fin_score, self.fin_raw, self.fin_len, self.fin_filled, self.parent):
+                ops.zero_(t_)
+            self.run.fill_(-1.0e9)
+            self.run.view(B, K)[:, 0] = 0.0
+            self.open.fill_(1)
 
 
 @dataclass
@@ -1454,11 +1479,12 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------
     # greedy decode  (HF generate: num_beams=1, do_sample=False, use_cache=True), and sampled decode (do_sample=True: temperature,
-    # top-k, top-p; num_return_sequences = K rows per question over ONE copy of the question's encoder states)
+    # top-k, top-p; num_return_sequences = K rows per question over ONE copy of the question's encoder states), and beam search
+    # (num_beams = K: the beams are those K rows; selection, bookkeeping and cache reordering on the device, csrc/beam.hip)
     # ------------------------------------------------------------------------------------------
     def generate(self, input_ids, attention_mask, max_length: int, capture_scores: bool = False, lengths=None, *, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_return_sequences: int = 1, seed=None,
-                 return_scores: bool = False):
+                 return_scores: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping: bool = False):
         """Defaults: the greedy decode, int64 [B, <= max_length].  do_sample / return_scores switch the last launch of a step from
         lako_greedy_step to lako_sample_step (greedy with scores: top_k = 1) and the decoder-side buffers to B·K rows, K =
         num_return_sequences: row b·K + k is answer k of question b (HF's layout).  The encoder runs once for the B questions and its
@@ -1466,14 +1492,26 @@ class Engine:
         return_scores adds float32 [B, K]: Σ over a row's emitted tokens (its EOS included, the pads after it not) of
         log_softmax(raw logits)[token] — the model's own log-probability, what `score` returns for that sequence; HF's transition scores
         are those of the PROCESSED distribution (temperature applied, truncated tokens at −∞), which say how likely the sampler was to
-        pick the token, not how likely the model finds the answer — the quantity a re-ranker wants is the latter."""
-        K, sampled = int(num_return_sequences), bool(do_sample or return_scores)
-        self._check_generate_args(do_sample, temperature, top_k, top_p, num_return_sequences, capture_scores)
+        pick the token, not how likely the model finds the answer — the quantity a re-ranker wants is the latter.
+
+        num_beams = K > 1: beam search with the semantics of transformers 5.15 `_beam_search` (include/lako_hip.h restates them), all
+        on the device: the decoder side has B·K rows, the last launches of a step are lako_beam_rows → lako_beam_merge →
+        lako_beam_gather, and the K beams of a question are K query positions of its cross-attention (the encoder states are neither
+        replicated nor reordered).  Returns int64 [B·R, <= max_length], R = num_return_sequences <= K: question b in rows b·R … b·R+R−1,
+        best finished hypothesis first, cropped to the longest returned row, pad after each row's EOS (HF 5.15 fills with EOS where
+        pad is 0: not reproduced).  Equal candidates go by ascending flat index beam·V + token (torch.topk leaves ties open).
+        return_scores adds float32 [B, R]: the RAW sum of log-probabilities, as above — HF's `sequences_scores`, the value the
+        hypotheses are ranked by, is raw / len**length_penalty with len = the number of generated tokens (EOS included)."""
+        self._check_generate_args(do_sample, temperature, top_k, top_p, num_return_sequences, capture_scores, num_beams, length_penalty,
+                                  early_stopping)
+        beam = int(num_beams) > 1
+        K, sampled = int(num_beams if beam else num_return_sequences), bool(do_sample or return_scores) and not beam
         if self.shadows_stale:
             self.refresh_shadows()
         B, N, L = input_ids.shape
-        ws = self._workspace(("gen", B, N, L, max_length) + ((K, "s") if sampled else ()))
+        ws = self._workspace(("gen", B, N, L, max_length) + ((K, "b") if beam else (K, "s") if sampled else ()))
         sparams = self._sampler_params(ws, do_sample, temperature, top_k, top_p, seed) if sampled else None
+        bparams = self._beam_params(ws, length_penalty, early_stopping) if beam else None
         # cross-attention in the encoder-state space (R = H query rows per sample and step; no K/V projection of the N·L encoder
         # states): five launches per layer and step instead of one — slower while the host's launch rate bounds the loop (eager:
         # 113 ms against 93 ms for 50 tokens at config 2), faster once a step is one graph launch.  Never when the raw scores are
@@ -1484,8 +1522,16 @@ class Engine:
         # valid tokens only (as in forward_loss) unless the raw scores are captured: those are laid out per padded position
         bt, enc_out, kv = self._batch(ws, input_ids, attention_mask, lengths, rows_q=K * self.cfg.num_heads if use_x else None, T=max_length,
                          keep_padding=capture_scores)
-        g = _GenState(self, ws, bt, enc_out, kv, max_length, K, sampled, capture_scores, sparams)
+        g = _GenState(self, ws, bt, enc_out, kv, max_length, K, sampled, capture_scores, sparams, bparams)
         n_out = self._gen_drive(g, lambda t: self._gen_step(g, t), use_graph)
+        if beam:
+            # the finished set is frozen from the step that ended the decoding (step n_out − 2, which wrote set (n_out − 1) & 1; a later
+            # step only copies it on).  One host read — the longest returned row — crops the result.
+            R = int(num_return_sequences)
+            fin = g.fin2[(n_out - 1) & 1].view(B, K, max_length)[:, :R]
+            width = max(1, min(max_length, int(g.fin_len.view(B, K)[:, :R].max())))
+            out = fin[:, :, :width].reshape(B * R, width).clone()
+            return (out, g.fin_raw.view(B, K)[:, :R].clone()) if return_scores else out
         out = g.seq[:, :n_out].clone()
         if capture_scores:
             # [B, H, n_layers, S] — the layout get_crossattention_scores builds with torch.cat(dim=2), src/model.py:152-160
@@ -1493,9 +1539,30 @@ class Engine:
             return (out, cs, g.score.view(B, K).clone()) if return_scores else (out, cs)
         return (out, g.score.view(B, K).clone()) if return_scores else out
 
-    def _check_generate_args(self, do_sample, temperature, top_k, top_p, num_return_sequences, capture_scores):
+    def _check_generate_args(self, do_sample, temperature, top_k, top_p, num_return_sequences, capture_scores, num_beams=1,
+                             length_penalty=1.0, early_stopping=False):
         """the argument errors of generate: raised before anything runs"""
         K = int(num_return_sequences)
+        if isinstance(num_beams, bool) or not isinstance(num_beams, (int, np.integer)) or num_beams < 1:
+            raise ValueError(f"num_beams must be an integer >= 1, got {num_beams!r}")
+        NB = int(num_beams)
+        if NB > 16:
+            raise ValueError(f"num_beams must be <= 16, got {num_beams}")
+        if NB > 1 and 2 * NB > self.cfg.vocab_size:
+            raise ValueError(f"num_beams = {NB} needs 2·num_beams <= vocab_size = {self.cfg.vocab_size} candidates per row")
+        if not isinstance(early_stopping, bool):
+            raise ValueError(f"early_stopping must be a bool, got {early_stopping!r}")
+        if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float, np.integer, np.floating)) or \
+                not float(length_penalty) == float(length_penalty):
+            raise ValueError(f"length_penalty must be a number, got {length_penalty!r}")
+        if NB > 1 and do_sample:
+            raise ValueError("num_beams > 1 with do_sample=True: beam search does not sample")
+        if NB > 1 and capture_scores:
+            raise ValueError("num_beams > 1 while the cross-attention scores are captured: the capture belongs to the greedy decode")
+        if NB > 1 and self.cfg.legacy_cross_bias:
+            raise ValueError("num_beams > 1 is not implemented with legacy_cross_bias")
+        if NB > 1 and K > NB:
+            raise ValueError(f"num_return_sequences = {K} must be <= num_beams = {NB}")
         if not temperature > 0:
             raise ValueError(f"temperature must be > 0, got {temperature}")
         if not 0 < top_p <= 1:
@@ -1504,11 +1571,11 @@ class Engine:
             raise ValueError(f"top_k must be an integer >= 0, got {top_k}")
         if K < 1:
             raise ValueError(f"num_return_sequences must be >= 1, got {num_return_sequences}")
-        if K > 1 and not do_sample:
-            raise ValueError("num_return_sequences > 1 needs do_sample=True: greedy decoding has one answer per question")
+        if K > 1 and not do_sample and NB == 1:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True or num_beams > 1: greedy decoding has one answer per question")
         if do_sample and capture_scores:
             raise ValueError("do_sample=True while the cross-attention scores are captured: the capture belongs to the greedy decode")
-        if K > 1 and self.cfg.legacy_cross_bias:
+        if K > 1 and NB == 1 and self.cfg.legacy_cross_bias:
             raise ValueError("num_return_sequences > 1 is not implemented with legacy_cross_bias")
 
     def _sampler_params(self, ws, do_sample, temperature, top_k, top_p, seed):
@@ -1526,16 +1593,28 @@ class Engine:
         sparams.copy_(ws["g.sparams_host"], non_blocking=True)
         return sparams
 
+    def _beam_params(self, ws, length_penalty, early_stopping):
+        """Beam search's per-call settings, in device memory at a stable address like the sampler's (captured steps replay under other
+        settings); the token column and "this is the last step" are arguments baked into each step's graph.  → int32 [8] `g.bparams`"""
+        words = np.array([np.float32(length_penalty).view(np.uint32), int(early_stopping), 0, 0, 0, 0, 0, 0], dtype=np.uint32)
+        bparams = self._buf(ws, "g.bparams", (8,), torch.int32)
+        if "g.bparams_host" not in ws:
+            ws["g.bparams_host"] = torch.zeros(8, dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        ws["g.bparams_host"].copy_(torch.from_numpy(words.view(np.int32)))      # (the last call ended with a wait on its last step)
+        bparams.copy_(ws["g.bparams_host"], non_blocking=True)
+        return bparams
+
     def _gen_step(self, g, t):
         """enqueue decode step t (reads nxt, writes seq[:, t + 1], nxt, done, ndone[t]): a decoder block per layer over the key / value
-        cache (not _dec_layer_fwd: other buffer lifetimes, other kernels), final norm, LM head, the greedy or sampling kernel"""
+        cache (not _dec_layer_fwd: other buffer lifetimes, other kernels), final norm, LM head, the greedy or sampling kernel — or beam
+        search's three (the step runs on cache set t & 1 and leaves the next step's rows, reordered by parent beam, in the other)"""
         ops, cfg = self.ops, self.cfg
         inner, H, dk = cfg.inner_dim, cfg.num_heads, cfg.d_kv
         BK, ML, h, h1, h2, xn, rs, c1, qc, c2, a1 = g.BK, g.ML, g.h, g.h1, g.h2, g.xn, g.rs, g.c1, g.qc, g.c2, g.a1
         ops.embed_fwd(g.nxt, self.shared.w, h)
         xkw = g.keys[2] if g.xrel is None else dict(g.keys[2], rel_bias=g.xrel, rel_off=ML - 1 - (0 if g.capture else t))
         for i, lw in enumerate(self.dec):
-            cache = g.cache[i]
+            cache = g.cache2[t & 1][i] if g.beam else g.cache[i]
             self._dec_norm_gemm(h, lw["ln1"].p, xn, rs, lw["qkv"].w, cache.view(BK, ML * 3 * inner)[:, t * 3 * inner:(t + 1) * 3 * inner])
             qs = cache[:, t:t + 1, :inner].unflatten(2, (H, dk))
             kc = cache[:, :t + 1, inner:2 * inner].unflatten(2, (H, dk))
@@ -1552,7 +1631,16 @@ class Engine:
             ops.gemm_nt(a1, lw["wo"].w, h, resid=h2)
         ops.rmsnorm_fwd(h, self.dec_final.p, xn, rs, cfg.layer_norm_epsilon)
         ops.gemm_nt(xn, self.lm_head.w, g.logits, alpha=self.head_alpha)
-        if g.sampled:
+        if g.beam:
+            src, dst = t & 1, (t + 1) & 1
+            ops.beam_rows(g.logits, g.run, g.cand_acc, g.cand_tok)
+            ops.beam_merge(g.cand_acc, g.cand_tok, g.seq2[src], g.seq2[dst], g.fin2[src], g.fin2[dst], t + 1, t + 2 == ML, g.run, g.nxt,
+                           g.parent, g.fin_score, g.fin_raw, g.fin_len, g.fin_filled, g.open, g.ndone[t:t + 1], g.bparams, cfg.eos_token_id,
+                           cfg.pad_token_id)
+            # (nothing runs after the last step; the gather's 16-byte unit always divides a cache row: d_kv is 32, 64 or 128 — Engine.__init__)
+            if t + 2 < ML:
+                ops.beam_gather(g.bcache[src], g.bcache[dst], g.parent, t + 1, inner, 2 * inner)
+        elif g.sampled:
             ops.sample_step(g.logits, g.seq, t + 1, g.nxt, g.done, g.score, g.ndone[t:t + 1], g.sparams, t, g.K, cfg.eos_token_id,
                             cfg.pad_token_id)
         else:

@@ -215,9 +215,13 @@ class FiDT5(nn.Module):
         loss, logits = _LossFn.apply(self._params_by_plain["shared.weight"], self, ids, mask, labels, passage_lengths)
         return FiDOutput(loss, logits)
 
+    # what `generate` uses where its caller passes None: {"num_beams": K, "length_penalty": p}.  The evaluation drivers' --num_beams /
+    # --length_penalty land here (lako_amd.options.Options.parse); assign a dict to an instance to set it for one model only.
+    generation_defaults: dict = {}
+
     @torch.no_grad()
     def generate(self, input_ids, attention_mask, max_length, passage_lengths=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
-                 num_return_sequences=1, seed=None, return_scores=False):
+                 num_return_sequences=1, seed=None, return_scores=False, num_beams=None, length_penalty=None, early_stopping=False):
         """src/model.py:54-60 → greedy decode, int64 [B, ≤max_length] with the leading start token.
 
         The sampling arguments of HF `generate` (extension; the defaults are the greedy decode above, launch for launch):
@@ -232,13 +236,32 @@ class FiDT5(nn.Module):
         log_softmax(raw logits)[token] — what `score` returns for that sequence.  Unlike HF's transition scores it is the model's own
         log-probability: temperature and truncation shape which token is drawn, not the score.  Works with do_sample=False (K = 1) too.
         ValueError: temperature ≤ 0, top_p outside (0, 1], top_k < 0, K < 1, K > 1 without do_sample, do_sample while cross-attention
-        scores are captured, K > 1 with legacy_cross_bias."""
+        scores are captured, K > 1 with legacy_cross_bias.
+
+        `num_beams=K > 1`: beam search, the semantics of transformers 5.15 (`length_penalty`, `early_stopping` ∈ {False, True} as there),
+        with the beams kept on the device and ONE encoder pass: the K beams of a question are K decoder rows over the question's one
+        set of encoder states.  Returns int64 [B·R, ≤max_length], R = `num_return_sequences` ≤ K: question b's R best finished
+        hypotheses in rows b·R … b·R+R−1, best first, cropped to the longest returned row.  Two deliberate differences from HF: the
+        columns after a row's EOS hold pad (HF 5.15 fills them with EOS when pad is 0), and `return_scores=True` gives float32 [B, R]
+        RAW sums of log-probabilities (what `score` returns for the sequence) — the ranking value, HF's `sequences_scores`, is
+        raw / len**length_penalty with len the number of generated tokens, EOS included.  Equal candidates are taken by ascending flat
+        index beam·V + token (torch.topk leaves ties open).  ValueError: num_beams > 16, 2·num_beams > vocab_size, num_beams > 1 with
+        do_sample, with captured cross-attention scores or with legacy_cross_bias, R > K, early_stopping not a bool.  `num_beams=None` /
+        `length_penalty=None` (the defaults) take `self.generation_defaults` — empty (greedy, 1.0) unless a driver or the caller set it:
+        a dict on the class for the process, or on an instance for that model."""
         self.n_passages = input_ids.size(1)
         eng = self._get_engine()
         skw = {}
         if do_sample or return_scores or num_return_sequences != 1 or temperature != 1.0 or top_k != 0 or top_p != 1.0:
             skw = dict(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, num_return_sequences=num_return_sequences,
                        seed=seed, return_scores=return_scores)
+        # (None: the model's generation defaults — `FiDT5.generation_defaults`, what the drivers' --num_beams / --length_penalty set)
+        num_beams = self.generation_defaults.get("num_beams", 1) if num_beams is None else num_beams
+        length_penalty = self.generation_defaults.get("length_penalty", 1.0) if length_penalty is None else length_penalty
+        if type(num_beams) is not int or num_beams != 1 or length_penalty != 1.0 or early_stopping is not False:
+            skw.update(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, num_return_sequences=num_return_sequences,
+                       seed=seed, return_scores=return_scores, num_beams=num_beams, length_penalty=length_penalty,
+                       early_stopping=early_stopping)
         if self._capture_scores and self._score_storage is None:
             out, scores, *rest = eng.generate(input_ids, attention_mask, max_length, capture_scores=True, **skw)
             self._score_storage = scores

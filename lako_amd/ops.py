@@ -976,3 +976,51 @@ class HipOps:
         self._timed("sample_step", 0.0, lambda: check(self.lib.lako_sample_step(
             _p(logits), V, rows, int(group), _p(seq), seq.stride(0), int(pos), _p(next_ids), _p(done), _p(score), _p(n_done), _p(params),
             int(step), int(eos_id), int(pad_id), self._stream()), "lako_sample_step"))
+
+    def beam_rows(self, logits, run, cand_acc, cand_tok):
+        """the rows' best candidates of a beam-search step (lako_beam_rows): logits fp32 [rows, V], run fp32 [rows] → cand_acc fp32 /
+        cand_tok int32 [rows, C]: each row's C best tokens, (x descending, index ascending), as (run + log-prob, token)"""
+        rows, V = logits.shape
+        C = cand_acc.shape[-1]
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or run.dtype != torch.float32 or run.numel() != rows or \
+                cand_acc.dtype != torch.float32 or cand_tok.dtype != torch.int32 or cand_acc.shape != (rows, C) or cand_tok.shape != (rows, C) or \
+                not (run.is_contiguous() and cand_acc.is_contiguous() and cand_tok.is_contiguous()):
+            raise LakoError("beam_rows: logits fp32 [rows, V], run fp32 [rows], cand_acc fp32 / cand_tok int32 [rows, C], all contiguous")
+        self._timed("beam_rows", 0.0, lambda: check(self.lib.lako_beam_rows(_p(logits), V, rows, C, _p(run), _p(cand_acc), _p(cand_tok),
+                                                                            self._stream()), "lako_beam_rows"))
+
+    def beam_merge(self, cand_acc, cand_tok, seq_src, seq_dst, fin_src, fin_dst, pos, last, run, next_ids, parent, fin_score, fin_raw, fin_len,
+                   fin_filled, open_, n_done, params, eos_id=1, pad_id=0):
+        """the questions' side of a beam-search step (lako_beam_merge): candidates [B·K, 2K] → next running beams (run, next_ids, parent,
+        token rows seq_src → seq_dst), the finished set (fin_src → fin_dst and its scores / lengths / flags), open [B], n_done[0] += K per
+        question that is done.  params int32 [8] on the device: length_penalty's float bits, early_stopping"""
+        BK, C = cand_acc.shape
+        K, ld = C // 2, seq_src.shape[1]
+        B = BK // max(K, 1)
+        i64s, f32s = (seq_src, seq_dst, fin_src, fin_dst), (cand_acc, run, fin_score, fin_raw)
+        if C != 2 * K or B * K != BK or cand_tok.shape != (BK, C) or cand_tok.dtype != torch.int32 or \
+                any(t.dtype != torch.int64 or t.shape != (BK, ld) or not t.is_contiguous() for t in i64s) or \
+                any(t.dtype != torch.float32 or not t.is_contiguous() for t in f32s) or any(t.numel() != BK for t in f32s[1:]) or \
+                next_ids.dtype != torch.int64 or next_ids.numel() != BK or parent.dtype != torch.int32 or parent.numel() != BK or \
+                fin_len.dtype != torch.int32 or fin_len.numel() != BK or fin_filled.dtype != torch.uint8 or fin_filled.numel() != BK or \
+                open_.dtype != torch.uint8 or open_.numel() != B or n_done.dtype != torch.int32 or params.dtype != torch.int32 or \
+                params.numel() < 8 or not cand_tok.is_contiguous():
+            raise LakoError("beam_merge: candidates [B·K, 2K] (fp32 / int32), token rows int64 [B·K, ld] contiguous, per-row state of B·K "
+                            "entries, open uint8 [B], params int32 [8]")
+        self._timed("beam_merge", 0.0, lambda: check(self.lib.lako_beam_merge(
+            _p(cand_acc), _p(cand_tok), B, K, _p(seq_src), _p(seq_dst), _p(fin_src), _p(fin_dst), ld, int(pos), int(bool(last)), _p(run),
+            _p(next_ids), _p(parent), _p(fin_score), _p(fin_raw), _p(fin_len), _p(fin_filled), _p(open_), _p(n_done), _p(params), int(eos_id),
+            int(pad_id), self._stream()), "lako_beam_merge"))
+
+    def beam_gather(self, src, dst, parent, n_pos, col0, width):
+        """dst[l, r, :n_pos, col0:col0 + width] = src[l, parent[r], :n_pos, col0:col0 + width] (lako_beam_gather): src / dst
+        [layers, rows, positions, columns] contiguous, distinct, of one dtype; parent int32 [rows]"""
+        if src.dim() != 4 or src.shape != dst.shape or src.dtype != dst.dtype or not (src.is_contiguous() and dst.is_contiguous()) or \
+                parent.dtype != torch.int32 or parent.numel() != src.shape[1] or not 0 < n_pos <= src.shape[2] or col0 < 0 or width <= 0 or \
+                col0 + width > src.shape[3]:
+            raise LakoError("beam_gather: src / dst [layers, rows, positions, columns] contiguous of one dtype, parent int32 [rows]")
+        Ld, rows, P, cols = src.shape
+        es = src.element_size()
+        self._timed("beam_gather", 0.0, lambda: check(self.lib.lako_beam_gather(
+            _p(src), _p(dst), _p(parent), Ld, rows, int(n_pos), rows * P * cols * es, P * cols * es, cols * es, int(col0) * es, int(width) * es,
+            self._stream()), "lako_beam_gather"))

@@ -64,6 +64,14 @@ class Options:
         p = self.parser
         p.add_argument("--write_results", action="store_true")
         p.add_argument("--write_crossattention_scores", action="store_true")
+        return self.add_decode_options()
+
+    def add_decode_options(self):
+        """(addition) how the evaluation decodes; the defaults are the reference's greedy decode.  test_reader.py gets them with its
+        eval options, train_reader.py adds them for its dev-set evaluation; `parse` hands them to the model class as generation defaults"""
+        p = self.parser
+        p.add_argument("--num_beams", type=int, default=1, help="beam search in the evaluation's generate; 1 = greedy")
+        p.add_argument("--length_penalty", type=float, default=1.0, help="beam search ranks hypotheses by log-prob / len**length_penalty")
         return self
 
     def add_reader_options(self):
@@ -104,4 +112,13 @@ class Options:
         return self
 
     def parse(self, argv=None):
-        return self.parser.parse_args(argv)
+        opt = self.parser.parse_args(argv)
+        if hasattr(opt, "num_beams"):
+            # raised before anything runs; the drivers' generate calls pass no decoding arguments: they take the model's defaults
+            if opt.num_beams < 1:
+                raise ValueError(f"--num_beams must be >= 1, got {opt.num_beams}")
+            if opt.num_beams > 1 and getattr(opt, "write_crossattention_scores", False):
+                raise ValueError("--write_crossattention_scores with --num_beams > 1: the captured scores belong to the greedy decode")
+            from .model import FiDT5
+            FiDT5.generation_defaults = dict(num_beams=opt.num_beams, length_penalty=opt.length_penalty) if opt.num_beams > 1 else {}
+        return opt

@@ -67,7 +67,7 @@ def json_loader(opt, ds, tokenizer, device, shuffle, with_index=False):
 
 
 def evaluate(model, batches, opt, tokenizer=None, dataset=None):
-    """Greedy decode (max_length 50) and score (train_reader.py:123-169).  With a tokenizer and the JSON dataset:
+    """Greedy decode — or beam search, the best hypothesis: `--num_beams`, through the model's generation defaults — (max_length 50) and score (train_reader.py:123-169).  With a tokenizer and the JSON dataset:
     the reference's soft exact match `ems(decoded answer, example['answer'])` (src/evaluation.py:158).  On synthetic
     batches (no tokenizer, no strings): exact match of the generated ids against the label ids."""
     from lako_amd import evaluation as E
@@ -91,7 +91,7 @@ def evaluate(model, batches, opt, tokenizer=None, dataset=None):
 
 
 def main():
-    opt = Options().add_reader_options().add_optim_options().parse()
+    opt = Options().add_reader_options().add_optim_options().add_decode_options().parse()
     opt.world_size = int(os.environ.get("WORLD_SIZE", "1"))
     opt.global_rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", opt.gpu if opt.local_rank < 0 else opt.local_rank))
