@@ -286,6 +286,24 @@ class _Ctx:
     ws: dict = field(default_factory=dict)
 
 
+# dW += dYᵀ·X — weight → the forward's saved input X ("e." + name + slot); the decoder: (dY's full-batch scratch, X), "d." + name + layer
+_ENC_DW_X = dict(wo="a1", wi="xn2", o="ctx", qkv="xn1")
+_DEC_DW = dict(wo=("dy.ffn", "a1"), wi=("dpre", "xn3"), co=("dy.c", "cctx"), cq=("dqc", "xn2"), o=("dy", "ctx"), qkv=("dqkv", "xn1"))
+
+
+@dataclass
+class _BwdPlan:
+    """What one Engine.backward call does where it has a choice, decided once at the top of the call (Engine._bwd_plan)"""
+    p: float             # the step's dropout rate
+    fused: bool          # every RMSNorm backward also writes dropout_bwd(dx) for the branch that consumes dx next; LAKO_FUSE_DROP=0: dropout_apply launches (A/B)
+    defer: bool          # the decoder's weight gradients in grouped launches after the chains; LAKO_DEC_DEFER_DW=0: inside the chain, on its rows (A/B)
+    hb_defer: bool       # the decoder's head-batched Wk / Wv gradient products in ONE launch after the chains (_dec_bwd)
+    grp: int             # encoder layers per grouped weight-gradient launch
+    enc_split: int       # the K-splits of that launch
+    fuse_gated: bool     # LAKO_FUSE_GATED (_fuse_gated)
+    one: int             # split_k of a one-split product that may be a gradient's first writer: −2 overwrites, −1 adds
+
+
 class Engine:
     def __init__(self, cfg: FiDConfig, ops, device, dtype=torch.bfloat16, seed: int = 0, fp8: bool | None = None):
         if cfg.d_kv not in (32, 64, 128):
@@ -463,14 +481,16 @@ class Engine:
         self.ops.mx_quantize(x, xq, xs)
         self.ops.gemm_nt_mx(xq, xs, w8[0], w8[1], out, **epi)
 
-    def _fuse_gated(self, x, w, f):
+    def _fuse_gated(self, x, w, f, fuse=None):
         """the encoder's gated-GELU products where the library's fused epilogues take the shape: "four" (LAKO_FUSE_GATED=0, the default):
         the four-wave product + the standalone kernel, or "fused" (=1): both in the product's epilogue — bit-identical, measured slower
         (0.895 against 0.721 ms per encoder layer at v1_1-base).  None (the decoder's skinny products, other shapes, the CPU
-        test double): the library's plain product + the standalone kernel."""
+        test double): the library's plain product + the standalone kernel.  `fuse`: the switch as the caller read it (_BwdPlan)."""
         if not hasattr(self.ops, "gemm_nt_gated") or not self.ops.gated_fused_ok(x, w, f):
             return None
-        return "fused" if os.environ.get("LAKO_FUSE_GATED", "0") == "1" else "four"
+        if fuse is None:
+            fuse = os.environ.get("LAKO_FUSE_GATED", "0") == "1"
+        return "fused" if fuse else "four"
 
     def zero_grad(self):
         self.ops.zero_(self.G)
@@ -1086,101 +1106,71 @@ class Engine:
         if i == Ld - 1:
             ops.rmsnorm_fwd(h_out, self.dec_final.p, ws["d.out"][ch["r0"]:ch["r1"]], ws["d.rsf"][ch["r0"]:ch["r1"]], eps, dr(S_DEC_FINAL))
 
-    def _dec_layer_bwd(self, ws, tmp, i, ch, dh_all, drel, kv, dkv, fused, T, S, dw_all):
+    def _dec_layer_bwd(self, ws, tmp, i, ch, dh_all, bw, drel, dxrel, dkv, T, S, dw_all, hb_all):
         """Backward of _dec_layer_fwd on the rows of one chain; dh_all [B·T, d] holds the gradient wrt the block's output on entry and
-        wrt its input on exit.  With dropout on, the six weight-gradient problems of the block are NOT launched here: their operands
-        (the dropped residual-branch gradients, dpre, dqc, dqkv) live in per-layer scratch, and the chain that handles the batch's last
-        rows appends the FULL-batch problems to `dw_all` — one grouped launch over all rows and layers after the chains have joined."""
+        wrt its input on exit.  With dropout on (bw.defer), the six weight-gradient problems of the block are NOT launched here: their
+        operands (the dropped residual-branch gradients, dpre, dqc, dqkv) live in per-layer scratch, and the chain that handles the
+        batch's last rows appends the FULL-batch problems to `dw_all` — one grouped launch over all rows and layers after the chains
+        have joined; `hb_all` (bw.hb_defer) collects the Wk / Wv gradient products likewise.  `dxrel`: legacy_cross_bias's gradient table."""
         cfg, ops, lw, dr = self.cfg, self.ops, self.dec[i], ch["dr"]
-        d, f, inner, H = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads
-        Bc, r0, r1 = ch["B"], ch["r0"], ch["r1"]
-        Md, p, Ld = dh_all.shape[0], (0.0 if dr(0) is None else dr(0)[0]), cfg.num_decoder_layers
+        d, f, inner, Bc, r0, r1 = cfg.d_model, cfg.d_ff, cfg.inner_dim, ch["B"], ch["r0"], ch["r1"]
+        Md, Ld, p, fused = dh_all.shape[0], cfg.num_decoder_layers, bw.p, bw.fused
         sl = lambda t: t[r0:r1]                                                                   # noqa: E731
         R = lambda name, cols: self._rows(tmp, name, ch, (Md, cols))                              # noqa: E731
+        per = f".{i}" if bw.defer else ""      # (operands of the deferred launches: scratch per layer)
         dh = sl(dh_all)
-        defer = p > 0 and os.environ.get("LAKO_DEC_DEFER_DW", "1") != "0"      # 0: launch them inside the chain, on its rows (A/B)
-        last = r1 == Md          # (this chain's call is the one that registers the full-batch weight-gradient problems)
         if i == Ld - 1:          # final norm of the decoder: dout (gradient wrt the normed, dropped output) → dh
             ops.rmsnorm_bwd(sl(tmp["d.dxn"]), sl(ws[f"d.h{Ld}"]), self.dec_final.p, sl(ws["d.rsf"]), None, dh, self.dec_final.g, dr(S_DEC_FINAL),
                             **self._nxt((R(f"d.dy.ffn.{i}", d), dr(_dec_site(i, 5))) if fused else None))
-
-        def wgrad(name, dy_name, dy_c, x_all, g):
-            """dW += dyᵀ·x: deferred to the grouped launch (full-batch operands) or launched on the chain's rows"""
-            if defer:
-                if last:
-                    dw_all.append((tmp[dy_name], x_all, g, 1.0))
-            else:
-                ops.gemm_tn(dy_c, sl(x_all), g)
-
-        # ---- FFN ------------------------------------------------------------------------------
-        if p > 0:
-            dy = R(f"d.dy.ffn.{i}", d)
-            if not fused:
-                ops.dropout_apply(dh, dy, dr(_dec_site(i, 5)))
-        else:
-            dy = dh
-        wgrad("wo", f"d.dy.ffn.{i}", dy, ws[f"d.a1.{i}"], lw["wo"].g)
-        if cfg.gated:      # dh = dy·Wo, then dpre = [da | db] of the gated activation (its dropout mask regenerated)
-            dha = R("d.dha", f)
-            ops.gemm_nt(dy, lw["wo"].wt, dha)
-            dpre = R(f"d.dpre.{i}" if defer else "d.dpre", 2 * f)
-            ops.gated_gelu_bwd(dha, sl(ws[f"d.pre.{i}"]), dpre, dr(_dec_site(i, 4)))
-        else:
-            dpre = R(f"d.dpre.{i}" if defer else "d.dpre", f)
-            ops.gemm_nt(dy, lw["wo"].wt, dpre, aux=sl(ws[f"d.a1.{i}"]), aux_scale=1.0 / (1.0 - p))
-        wgrad("wi", f"d.dpre.{i}", dpre, ws[f"d.xn3.{i}"], lw["wi"].g)
+        # dW[w] += dyᵀ·x: on the chain's rows now, or deferred (the full-batch problems: at the end of this function)
+        wgrad = (lambda w, dy: None) if bw.defer else (lambda w, dy: ops.gemm_tn(dy, sl(ws[f"d.{_DEC_DW[w][1]}.{i}"]), lw[w].g))
+        # ---- FFN: the decoder's skinny products never take the library's gated route, whatever their row count ----------------
+        dy_f = R(f"d.dy.ffn.{i}", d) if p > 0 else None
         dxn = R("d.dxn", d)
-        ops.gemm_nt(dpre, lw["wi"].wt, dxn)
+        if cfg.gated:
+            R("d.dha", f)      # (allocated ahead of dpre, as it always was here)
+        self._ffn_bwd(lw, dh, dy_f, sl(ws[f"d.a1.{i}"]), sl(ws[f"d.pre.{i}"]) if cfg.gated else None, bw, dr(_dec_site(i, 4)),
+                      dr(_dec_site(i, 5)), R, ("d.dpre" + per, "d.dha"), dxn, wgrad, library_gated=False)
         dy_c = R(f"d.dy.c.{i}", d) if p > 0 else None
         ops.rmsnorm_bwd(dxn, sl(ws[f"d.h2.{i}"]), lw["ln3"].p, sl(ws[f"d.rs3.{i}"]), dh, dh, lw["ln3"].g,
                         **self._nxt((dy_c, dr(_dec_site(i, 3))) if fused else None))
         # ---- cross-attention ---------------------------------------------------------------------
-        dy = dh
-        if p > 0:
-            dy = dy_c
-            if not fused:
-                ops.dropout_apply(dh, dy, dr(_dec_site(i, 3)))
-        wgrad("co", f"d.dy.c.{i}", dy, ws[f"d.cctx.{i}"], lw["co"].g)
-        hb = ch.get("hb") if ch["xa"] is not None else None      # the Wk / Wv gradient products of all layers in one launch (backward())
-        dctx = R(f"d.xdctx.{i}" if hb is not None else "d.dctx", inner)
+        dy = self._branch_grad(dh, dy_c, dr(_dec_site(i, 3)), fused)
+        wgrad("co", dy)
+        dctx = R(f"d.xdctx.{i}" if hb_all is not None else "d.dctx", inner)      # (hb_all: only with the encoder-state cross-attention)
         ops.gemm_nt(dy, lw["co"].wt, dctx)
-        dqc = R(f"d.dqc.{i}" if defer else "d.dqc", inner)
-        qc = sl(ws[f"d.qc.{i}"])
+        dqc, qc = R("d.dqc" + per, inner), sl(ws[f"d.qc.{i}"])
         if ch["xa"] is not None:
             self._xattn_bwd(ch["xb"], ch["xa"], tmp, i, qc, ws["e.out"], dctx, dqc, Bc, T, S, dr(_dec_site(i, 2)), b0=ch["b0"],
-                            B_all=Md // T, hb=hb)
+                            B_all=Md // T, hb=hb_all)
         else:
-            c2 = sl(ws[f"d.cctx.{i}"])
+            kv, c2, ckw = ws["e.kv"], sl(ws[f"d.cctx.{i}"]), (ch["ckw"] if dxrel is None else dict(ch["ckw"], drel=dxrel))
             ops.attn_bwd(self._heads(qc, Bc, T, 0), self._cross_kv(kv, ch, 2 * i * inner), self._cross_kv(kv, ch, (2 * i + 1) * inner),
                          self._heads(c2, Bc, T, 0), self._heads(dctx, Bc, T, 0), ws[f"d.cst.{i}"][ch["b0"]:ch["b1"]],
                          self._heads(dqc, Bc, T, 0), self._cross_kv(dkv, ch, 2 * i * inner), self._cross_kv(dkv, ch, (2 * i + 1) * inner),
-                         drop=dr(_dec_site(i, 2)), **ch["ckw"])
-        wgrad("cq", f"d.dqc.{i}", dqc, ws[f"d.xn2.{i}"], lw["cq"].g)
+                         drop=dr(_dec_site(i, 2)), **ckw)
+        wgrad("cq", dqc)
         ops.gemm_nt(dqc, lw["cq"].wt, dxn)
         dy_s = R(f"d.dy.{i}", d) if p > 0 else None
         ops.rmsnorm_bwd(dxn, sl(ws[f"d.h1.{i}"]), lw["ln2"].p, sl(ws[f"d.rs2.{i}"]), dh, dh, lw["ln2"].g,
                         **self._nxt((dy_s, dr(_dec_site(i, 1))) if fused else None))
         # ---- causal self-attention ---------------------------------------------------------------
-        dy = dh
-        if p > 0:
-            dy = dy_s
-            if not fused:
-                ops.dropout_apply(dh, dy, dr(_dec_site(i, 1)))
-        wgrad("o", f"d.dy.{i}", dy, ws[f"d.ctx.{i}"], lw["o"].g)
+        dy = self._branch_grad(dh, dy_s, dr(_dec_site(i, 1)), fused)
+        qkv, c1 = sl(ws[f"d.qkv.{i}"]), sl(ws[f"d.ctx.{i}"])
+        wgrad("o", dy)
         dctx = R("d.dctx", inner)      # (not the cross-attention's buffer: that one may be an operand of the deferred Wv-gradient launch)
         ops.gemm_nt(dy, lw["o"].wt, dctx)
-        qkv, c1 = sl(ws[f"d.qkv.{i}"]), sl(ws[f"d.ctx.{i}"])
-        dqkv = R(f"d.dqkv.{i}" if defer else "d.dqkv", 3 * inner)
+        dqkv = R("d.dqkv" + per, 3 * inner)
         ops.attn_bwd(self._heads(qkv, Bc, T, 0), self._heads(qkv, Bc, T, inner), self._heads(qkv, Bc, T, 2 * inner),
                      self._heads(c1, Bc, T, 0), self._heads(dctx, Bc, T, 0), ws[f"d.st.{i}"][ch["b0"]:ch["b1"]],
                      self._heads(dqkv, Bc, T, 0), self._heads(dqkv, Bc, T, inner), self._heads(dqkv, Bc, T, 2 * inner),
                      rel_bias=ws["d.rel"], drel=drel, rel_off=T - 1, causal=True, drop=dr(_dec_site(i, 0)))
-        wgrad("qkv", f"d.dqkv.{i}", dqkv, ws[f"d.xn1.{i}"], lw["qkv"].g)
+        wgrad("qkv", dqkv)
         ops.gemm_nt(dqkv, lw["qkv"].wt, dxn)
-        nxt = None
-        if fused and i > 0:
-            nxt = (R(f"d.dy.ffn.{i - 1}", d), dr(_dec_site(i - 1, 5)))
+        nxt = (R(f"d.dy.ffn.{i - 1}", d), dr(_dec_site(i - 1, 5))) if fused and i > 0 else None
         ops.rmsnorm_bwd(dxn, sl(ws[f"d.h{i}"]), lw["ln1"].p, sl(ws[f"d.rs1.{i}"]), dh, dh, lw["ln1"].g, **self._nxt(nxt))
+        if bw.defer and r1 == Md:      # (this chain's call is the one that registers the full-batch weight-gradient problems)
+            dw_all += [(tmp[f"d.{dy}.{i}"], ws[f"d.{x}.{i}"], lw[w].g, 1.0) for w, (dy, x) in _DEC_DW.items()]
         if i == 0:
             self._embed_bwd(ws["d.ids"].view(-1)[r0:r1], dh, dr(S_DEC_EMBED))
 
@@ -1274,72 +1264,107 @@ class Engine:
             a, b = self.by_name[first_block], self.by_name[last_block]
             self.grad_hook(a.off, b.off + -(-b.numel // ALIGN) * ALIGN)
 
-    def _ffn_bwd(self, lw, dh, a1, xn, h_in, rs, ln, p, drop_out, tmp, dw=None, dy_pre=None, nxt=None, role="d", slot="", pre=None,
-                 drop_act=None):
-        """residual FFN sublayer backward; dh is updated in place to the gradient wrt the sublayer input.
-        `dw`: list collecting the weight-gradient problems for one grouped launch (encoder layers with dropout: their
-        operands live in per-layer scratch that stays untouched until the layer's backward is complete).
-        `dy_pre`: dropout_bwd(dh) already written by the RMSNorm backward that produced dh; `nxt` = (buffer, dropout) asks
-        this sublayer's RMSNorm backward to do the same for the next consumer (saves a pass over the residual gradient).
-        `role` ("d" decoder / "e" encoder) names the scratch: by ROLE, never by row count — the unpadded encoder has a
-        different row count for almost every batch, and a size in the name would leave one dead buffer set per batch.
-        `pre` (gated-GELU feed-forward): the saved [a | b] product; `drop_act` the dropout of the activation."""
-        ops = self.ops
-        M, d = dh.shape
-        f = a1.shape[1]
-        dy = dh
-        if p > 0 and dy_pre is not None:
-            dy = dy_pre
-        elif p > 0:
-            dy = self._buf(tmp, f"{role}.dy.ffn{slot}" if dw is not None else f"{role}.dy", (M, d))
-            ops.dropout_apply(dh, dy, drop_out)
-        if dw is not None and p > 0:
-            dw.append((dy, a1, lw["wo"].g, 1.0))
-        else:
-            ops.gemm_tn(dy, a1, lw["wo"].g)
-        if pre is not None:
-            dpre = self._buf(tmp, f"{role}.dpre{slot}", (M, 2 * f))
-            fz = self._fuse_gated(dy, lw["wo"].wt, f)
-            if fz == "fused":      # dpre straight from the dY·Wo product's epilogue (bit-identical to the two launches below)
-                ops.gemm_nt_gated(dy, lw["wo"].wt, dpre, pre, drop_act, backward=True)
-            else:
-                dha = self._buf(tmp, f"{role}.dha", (M, f))
-                (ops.gemm_nt_four if fz else ops.gemm_nt)(dy, lw["wo"].wt, dha)
-                ops.gated_gelu_bwd(dha, pre, dpre, drop_act)
-        else:
-            dpre = self._buf(tmp, f"{role}.dpre{slot}", (M, f))
-            ops.gemm_nt(dy, lw["wo"].wt, dpre, aux=a1, aux_scale=1.0 / (1.0 - p))   # ∘ [relu'>0] ∘ dropout
-        if dw is not None:
-            dw.append((dpre, xn, lw["wi"].g, 1.0))
-        else:
-            ops.gemm_tn(dpre, xn, lw["wi"].g)
-        dxn = self._buf(tmp, f"{role}.dxn", (M, d))
-        ops.gemm_nt(dpre, lw["wi"].wt, dxn)
-        ops.rmsnorm_bwd(dxn, h_in, ln.p, rs, dh, dh, ln.g, **self._nxt(nxt))
-
     @staticmethod
     def _nxt(nxt):
         return {} if nxt is None else dict(dx_drop=nxt[0], drop_out=nxt[1])
 
+    def _bwd_plan(self, ctx):
+        """The one place backward reads the environment, at the time of the call (the A/B switches may change after forward_loss)"""
+        env, p = os.environ.get, ctx.p
+        fused = p > 0 and env("LAKO_FUSE_DROP", "1") != "0"
+        # WEIGHT GRADIENTS OF SEVERAL ENCODER LAYERS IN ONE LAUNCH (round 4).  A layer's four dW are 108 tiles of 256²; with two K-splits
+        # that is 216 workgroups on 256 CUs — every layer's launch leaves 16 % of the chip idle, and nothing can fill it (one workgroup
+        # per CU: 128 KiB of LDS).  The products do not have to run where their operands are produced: with the operands of `grp`
+        # layers kept in per-slot scratch (dy, dpre, dqkv: 0.66 GB per layer at config 2) their 108·grp tiles × splits go out as ONE grid
+        # that the dispatcher deals over the CUs as they free up — 12 layers × 2 splits = 2 592 units = 10.1 rounds of half-K units
+        # instead of 12 rounds.  Not with set_checkpoint (the forward operands of a layer are recomputed into ONE slot), not when a
+        # data-parallel hook wants every layer's gradients as soon as they exist (overlap mode; the deferred all-reduce does not), not
+        # without dropout (dy aliases the residual gradient then).
+        grouped = fused and not ctx.ckpt and not (self.grad_hook is not None and self.grad_ranges_early)
+        grp = max(1, min(int(env("LAKO_ENC_DW_GROUP", "12")), self.cfg.num_layers, 12)) if grouped else 1
+        return _BwdPlan(
+            p=p, fused=fused, grp=grp,
+            defer=p > 0 and env("LAKO_DEC_DEFER_DW", "1") != "0",
+            hb_defer=ctx.xa is not None and len(ctx.chains) == 1 and env("LAKO_DEC_HB_DEFER", "1") != "0",
+            # K-splits of the grouped launch: 3 (1 296 tiles × 3 = 15.2 rounds of third-K units; measured per step, rocprofv3, 14 steps:
+            # one launch per layer 8.70 ms, 12 layers × 2 / 3 / 4 splits 8.35 / 8.32 / 8.30 ms, 6 layers × 3 splits 8.35 — the library's
+            # own cost model, built for one-round launches, would pick 1 split = 6 whole rounds: the slowest, 41.3 ms per step)
+            # −3: the hybrid schedule of lako_gemm_tn_grouped — whole rounds of full-K tiles + a finely cut remainder (round 4: 39.8 → 39.1 ms
+            # per step against 3 uniform K-splits; a positive value forces that many uniform splits)
+            enc_split=int(env("LAKO_ENC_DW_SPLIT", "-3")),
+            fuse_gated=env("LAKO_FUSE_GATED", "0") == "1",
+            # (the FIRST writer of a freshly zeroed gradient buffer overwrites: no read at all; gradient accumulation adds)
+            one=-2 if self._g_fresh else -1)
+
+    def _branch_grad(self, dh, dy, drop, fused):
+        """The gradient into a residual branch whose output was dropped with `drop`, given the residual sum's gradient dh: dh itself without
+        dropout; else dropout_bwd(dh) in the scratch `dy` — written by the RMSNorm backward that produced dh (`fused`), or by a launch here."""
+        if drop is not None and not fused:
+            self.ops.dropout_apply(dh, dy, drop)
+        return dh if drop is None else dy
+
+    def _ffn_bwd(self, lw, dh, dy, a1, pre, bw, drop_act, drop_out, buf, names, dxn, wgrad, library_gated):
+        """Backward of a residual feed-forward sublayer up to its RMSNorm, of either stack: dh [rows, d] the gradient wrt the sublayer's
+        output, `dy` the scratch of _branch_grad → dxn, the gradient wrt the normed input.  What differs between the stacks:
+        `buf(name, cols)` and `names` of dpre and dha — the scratch of these rows: the encoder's per-slot buffers, a chain's rows of the
+        decoder's full-batch ones (named by role and slot, never by row count: the unpadded encoder's changes with almost every batch);
+        `wgrad(w, dy)` — where the problem dW[w] += dyᵀ·x goes: into a group, to the full-batch launch after the chains, or out now;
+        `library_gated` — whether to ask for the library's gated-GELU routes (_fuse_gated).  NOT the decoder: its skinny products stay
+        the plain product + the standalone kernel whatever their row count.
+        `pre` (gated-GELU feed-forward): the saved [a | b] product; `drop_act` the dropout of the activation, `drop_out` of the output."""
+        ops, f = self.ops, a1.shape[1]
+        dy = self._branch_grad(dh, dy, drop_out, bw.fused)
+        wgrad("wo", dy)
+        if pre is not None:
+            dpre = buf(names[0], 2 * f)
+            fz = self._fuse_gated(dy, lw["wo"].wt, f, bw.fuse_gated) if library_gated else None
+            if fz == "fused":      # dpre straight from the dY·Wo product's epilogue (bit-identical to the two launches below)
+                ops.gemm_nt_gated(dy, lw["wo"].wt, dpre, pre, drop_act, backward=True)
+            else:
+                dha = buf(names[1], f)
+                (ops.gemm_nt_four if fz else ops.gemm_nt)(dy, lw["wo"].wt, dha)
+                ops.gated_gelu_bwd(dha, pre, dpre, drop_act)
+        else:
+            dpre = buf(names[0], f)
+            ops.gemm_nt(dy, lw["wo"].wt, dpre, aux=a1, aux_scale=1.0 / (1.0 - bw.p))   # ∘ [relu'>0] ∘ dropout
+        wgrad("wi", dpre)
+        ops.gemm_nt(dpre, lw["wi"].wt, dxn)
+
     def backward(self, upstream=None):
         """Accumulate d(loss)/d(params) into G.  `upstream`: optional device scalar tensor multiplying the loss."""
-        ctx, cfg, ops = self.ctx, self.cfg, self.ops
+        ctx, ops = self.ctx, self.ops
         if ctx is None:
             raise RuntimeError("backward() without a preceding forward_loss()")
-        ws, p, seed = ctx.ws, ctx.p, ctx.seed
-        B, N, L, T = ctx.B, ctx.N, ctx.L, ctx.T
-        d, f, inner, H, V = cfg.d_model, cfg.d_ff, cfg.inner_dim, cfg.num_heads, cfg.vocab_size
-        rag = ctx.rag
-        self._row_cap = {rag.M: B * N * L} if rag is not None else {}
-        Md, Me, S, Ld, Le = B * T, (rag.M if rag is not None else B * N * L), N * L, cfg.num_decoder_layers, cfg.num_layers
+        bw = self._bwd_plan(ctx)
+        self._g_fresh = False
+        ws, p, seed, rag, L = ctx.ws, ctx.p, ctx.seed, ctx.rag, ctx.L
+        self._row_cap = {rag.M: ctx.B * ctx.N * L} if rag is not None else {}
+        Me = rag.M if rag is not None else ctx.B * ctx.N * L
         dr = (lambda site: (p, seed, site)) if p > 0 else (lambda site: None)
-        tmp = self._workspace(("bwd", B, N, L, T))
-        # ---- loss + LM head ------------------------------------------------------------------
-        dlog = self._buf(tmp, "dlogits", (Md, V))
+        tmp = self._workspace(("bwd", ctx.B, ctx.N, L, ctx.T))
+        dh = self._head_bwd(ws, tmp, ctx, bw, upstream)
+        xb, dkv = self._dec_bwd(ws, tmp, ctx, bw, dh, Me)
+        # ---- cross K/V projection of all decoder layers -----------------------------------------
+        deh, dxe = (self._buf(tmp, name, (Me, self.cfg.d_model)) for name in ("e.dh", "e.dxn"))
+        if ctx.xa is not None:
+            self._xattn_denc(xb, ctx.xa, tmp, Me, dxe)
+        else:
+            ops.gemm_tn(dkv, ws["e.out"], self.kv_all.g)
+            ops.gemm_nt(dkv, self.kv_all.wt, dxe)
+        # ---- encoder -----------------------------------------------------------------------------
+        self._enc_bwd(ws, tmp, ctx, bw, dr, deh, dxe)
+        self._embed_bwd(ctx.enc_ids, deh, dr(S_ENC_EMBED))
+        ops.relpos_reduce(tmp["e.drel"], self._lut(L, L, True), self.enc_rel.g)
+        self._ready("enc.rel", "shared")
+        self.step_count += 1   # next forward draws fresh dropout masks
+        self.ctx = None
+
+    def _head_bwd(self, ws, tmp, ctx, bw, upstream):
+        """loss + LM head: the gradient wrt the decoder's normed, dropped output in "d.dxn"; → the decoder's residual-gradient buffer"""
+        ops, Md, d, alpha, head = self.ops, ctx.B * ctx.T, self.cfg.d_model, self.head_alpha, self.lm_head
+        dlog = self._buf(tmp, "dlogits", (Md, self.cfg.vocab_size))
         ops.ce_fwd_bwd(ws["d.logits"], ctx.labels, self._buf(tmp, "loss2", (2,), torch.float32), dlog, upstream)
-        alpha, head = self.head_alpha, self.lm_head
-        dh = self._buf(tmp, "d.dh", (Md, d))
-        dout = self._buf(tmp, "d.dxn", (Md, d))
+        dh, dout = (self._buf(tmp, name, (Md, d)) for name in ("d.dh", "d.dxn"))
         # K = vocabulary (32128) for an [Md, d] output of a handful of tiles: accumulate in fp32 with atomics so that the
         # library may split K over the idle CUs (gemm_nt_ring_kernel), then round once to the compute dtype
         dout32 = dout if dout.dtype == torch.float32 else self._buf(tmp, "d.dout32", (Md, d), torch.float32)
@@ -1351,131 +1376,105 @@ class Engine:
             if dout32 is not dout:
                 ops.cast(dout32.view(-1), dout.view(-1))
         # (K = B·T rows, 378 tiles: one K-split; nothing else touches the embedding gradient until the embedding backward kernels later on
-        # this stream: plain read-modify-write instead of 99 MB of float atomics)
-        # (and the FIRST writer of a freshly zeroed gradient buffer overwrites: no read at all.  A second backward without zero_grad —
-        # gradient accumulation — adds)
-        one = -2 if self._g_fresh else -1
-        self._g_fresh = False
-        ops.gemm_tn(dlog, ws["d.out"], head.g, alpha=alpha, split_k=one)
+        # this stream: plain read-modify-write instead of 99 MB of float atomics; bw.one: the first writer overwrites)
+        ops.gemm_tn(dlog, ws["d.out"], head.g, alpha=alpha, split_k=bw.one)
         if head is not self.shared:
             self._ready("lm_head", "lm_head")
-        # every RMSNorm backward also writes dropout_bwd(dx) for the residual branch that consumes dx next (fused=True)
-        fused = p > 0 and os.environ.get("LAKO_FUSE_DROP", "1") != "0"   # 0: separate dropout_apply launches (A/B)
-        xa = ctx.xa
+        return dh
+
+    def _dec_bwd(self, ws, tmp, ctx, bw, dh, Me):
+        """The decoder's chains, last layer first, then what they left for after their join.  → (xb, dkv): what the encoder-state
+        gradient is assembled from (_xattn_buffers), or the gradient of the projected cross-attention K / V"""
+        ops, cfg, xa = self.ops, self.cfg, ctx.xa
+        B, N, L, T, H, Ld = ctx.B, ctx.N, ctx.L, ctx.T, cfg.num_heads, cfg.num_decoder_layers
         xb = self._xattn_buffers(ws, B, N, L, T, Ld, xa.splits) if xa is not None else None
-        dkv = kv = None
-        if xa is None:
-            dkv = self._buf(tmp, "dkv", (Me, self.kv_all.w.shape[0]))
-            kv = ws["e.kv"]
+        dkv = self._buf(tmp, "dkv", (Me, self.kv_all.w.shape[0])) if xa is None else None
         drel = self._buf(tmp, "d.drel", (H, 2 * T - 1), torch.float32)
         ops.zero_(drel)
         dxrel = None
-        if self.dec_xrel is not None:      # (the chains' key arguments were built in forward_loss without the gradient table)
+        if self.dec_xrel is not None:      # (_legacy_layout)
             dxrel = self._buf(tmp, "d.dxrel", (H, 2 * T - 1), torch.float32)
             ops.zero_(dxrel)
-            for ch in ctx.chains:
-                ch["ckw"] = dict(ch["ckw"], drel=dxrel)
         dw_all = []      # every decoder weight gradient of the step (K = B·T rows): grouped launches after the last layer
         # the 2 · Ld head-batched Wk / Wv gradient products likewise: ONE launch after the last layer (each alone is its dispatch: 24 × 8 µs);
         # with one chain only (LAKO_DEC_HB_DEFER=0: inside the layers)
-        hb_all = [] if (xa is not None and len(ctx.chains) == 1 and os.environ.get("LAKO_DEC_HB_DEFER", "1") != "0") else None
-        for ch in ctx.chains:
-            ch["hb"] = hb_all
-        self._run_chains(ctx.chains, Ld, lambda i, ch: self._dec_layer_bwd(ws, tmp, i, ch, dh, drel, kv, dkv, fused, T, S, dw_all),
-                         reverse=True)
+        hb_all = [] if bw.hb_defer else None
+        self._run_chains(ctx.chains, Ld, lambda i, ch: self._dec_layer_bwd(ws, tmp, i, ch, dh, bw, drel, dxrel, dkv, T, N * L,
+                                                                           dw_all, hb_all), reverse=True)
         if hb_all:
             ops.headbatch_tn_multi(hb_all)
         if dw_all:      # (K = B·T rows: one K-split; the chains have joined and nothing else touches these gradients: plain read-modify-write)
-            ops.gemm_tn_grouped(dw_all, split_k=one)
+            ops.gemm_tn_grouped(dw_all, split_k=bw.one)
         ops.relpos_reduce(drel, self._lut(T, T, False), self.dec_rel.g)
         if dxrel is not None:
             ops.relpos_reduce(dxrel, self._lut(T, T, False), self.dec_xrel.g)
-            for ch in ctx.chains:
-                ch["ckw"] = {k: v for k, v in ch["ckw"].items() if k != "drel"}
-        # ---- cross K/V projection of all decoder layers -----------------------------------------
-        deh = self._buf(tmp, "e.dh", (Me, d))
-        dxe = self._buf(tmp, "e.dxn", (Me, d))
-        if xa is not None:
-            self._xattn_denc(xb, xa, tmp, Me, dxe)
-        else:
-            ops.gemm_tn(dkv, ws["e.out"], self.kv_all.g)
-            ops.gemm_nt(dkv, self.kv_all.wt, dxe)
-        # WEIGHT GRADIENTS OF SEVERAL ENCODER LAYERS IN ONE LAUNCH (round 4).  A layer's four dW are 108 tiles of 256²; with two K-splits
-        # that is 216 workgroups on 256 CUs — every layer's launch leaves 16 % of the chip idle, and nothing can fill it (one workgroup
-        # per CU: 128 KiB of LDS).  The products do not have to run where their operands are produced: with the operands of `grp`
-        # layers kept in per-slot scratch (dy, dpre, dqkv: 0.66 GB per layer at config 2) their 108·grp tiles × splits go out as ONE grid
-        # that the dispatcher deals over the CUs as they free up — 12 layers × 2 splits = 2 592 units = 10.1 rounds of half-K units
-        # instead of 12 rounds.  Not with set_checkpoint (the forward operands of a layer are recomputed into ONE slot), not when a
-        # data-parallel hook wants every layer's gradients as soon as they exist (overlap mode; the deferred all-reduce does not), not
-        # without dropout (dy aliases the residual gradient then).
-        grp = 1
-        if fused and not ctx.ckpt and not (self.grad_hook is not None and self.grad_ranges_early):
-            grp = max(1, min(int(os.environ.get("LAKO_ENC_DW_GROUP", "12")), Le, 12))
-        # K-splits of the grouped launch: 3 (1 296 tiles × 3 = 15.2 rounds of third-K units; measured per step, rocprofv3, 14 steps:
-        # one launch per layer 8.70 ms, 12 layers × 2 / 3 / 4 splits 8.35 / 8.32 / 8.30 ms, 6 layers × 3 splits 8.35 — the library's
-        # own cost model, built for one-round launches, would pick 1 split = 6 whole rounds: the slowest, 41.3 ms per step)
-        # −3: the hybrid schedule of lako_gemm_tn_grouped — whole rounds of full-K tiles + a finely cut remainder (round 4: 39.8 → 39.1 ms per step
-        # against 3 uniform K-splits; a positive value forces that many uniform splits)
-        enc_split = int(os.environ.get("LAKO_ENC_DW_SPLIT", "-3"))
-        slot_of = (lambda i: f".{i % grp}") if grp > 1 else (lambda i: "")
-        dy_f = self._buf(tmp, "e.dy.ffn" + slot_of(Le - 1), (Me, d)) if fused else None
+        return xb, dkv
+
+    def _enc_bwd(self, ws, tmp, ctx, bw, dr, deh, dxe):
+        """The encoder's final norm and its layers, last first: dxe the gradient wrt the encoder's output → deh, wrt the embedding's.  The
+        weight gradients of bw.grp layers go out in ONE launch (_bwd_plan); a layer's are reported (_ready) once that launch is out."""
+        ops, Le, grp, fused, L, (Me, d) = self.ops, self.cfg.num_layers, bw.grp, bw.fused, ctx.L, deh.shape
+        slot = (lambda i: f".{i % grp}") if grp > 1 else (lambda i: "")      # a layer's scratch: one set per layer of a group
+        dy_f = self._buf(tmp, "e.dy.ffn" + slot(Le - 1), (Me, d)) if fused else None
         ops.rmsnorm_bwd(dxe, ws[f"e.h{Le}"], self.enc_final.p, ws["e.rsf"], None, deh, self.enc_final.g, dr(S_ENC_FINAL),
                         **self._nxt((dy_f, dr(_enc_site(Le - 1, 3))) if fused else None))
         self._ready("dec.final_ln", "enc.final_ln")
-        # ---- encoder ---------------------------------------------------------------------------
-        BN = B * N
-        drel_e = self._buf(tmp, "e.drel", (H, 2 * L - 1), torch.float32)
+        drel_e = self._buf(tmp, "e.drel", (self.cfg.num_heads, 2 * L - 1), torch.float32)
         ops.zero_(drel_e)
-        dw, dw_layers = [], []
-        for i in reversed(range(Le)):
-            lw = self.enc[i]
-            j, sl = i, slot_of(i)
-            if ctx.ckpt:   # recompute this block's intermediates from its saved input (same seeds → same dropout masks)
-                j = 0
-                self._enc_layer_fwd(ws, i, 0, ws[f"e.h{i}"], None, BN, L, ctx.enc_mask, ws["e.rel"], dr, rag)
-            # the layer's four weight gradients (K = all tokens, small M×N) go out in ONE grouped launch (with those of the other
-            # layers of its group): 108 tiles per layer fill the chip with ~2 K-splits, where four separate launches need 7–28 splits
-            # each and pay one fp32 atomic pass over the output per split
-            dy_s = self._buf(tmp, "e.dy" + sl, (Me, d)) if fused else None
-            self._ffn_bwd(lw, deh, ws[f"e.a1.{j}"], ws[f"e.xn2.{j}"], ws[f"e.h1.{j}"], ws[f"e.rs2.{j}"], lw["ln2"], p,
-                          dr(_enc_site(i, 3)), tmp, dw, dy_pre=dy_f, nxt=(dy_s, dr(_enc_site(i, 1))) if fused else None, role="e", slot=sl,
-                          pre=ws[f"e.pre.{j}"] if cfg.gated else None, drop_act=dr(_enc_site(i, 2)))
-            dy = deh
-            if p > 0:
-                dy = dy_s if fused else self._buf(tmp, "e.dy", (Me, d))
-                if not fused:
-                    ops.dropout_apply(deh, dy, dr(_enc_site(i, 1)))
-                dw.append((dy, ws[f"e.ctx.{j}"], lw["o"].g, 1.0))
-            else:
-                ops.gemm_tn(dy, ws[f"e.ctx.{j}"], lw["o"].g)     # dy aliases deh, which the next ops rewrite
-            dctx = self._buf(tmp, "e.dctx", (Me, inner))
-            ops.gemm_nt(dy, lw["o"].wt, dctx)
-            qkv = ws[f"e.qkv.{j}"]
-            dqkv = self._buf(tmp, "e.dqkv" + sl, (Me, 3 * inner))
-            hb, ht, akw = self._enc_attn_layout(rag, BN, L, ctx.enc_mask)
-            ops.attn_bwd(self._heads(qkv, hb, ht, 0), self._heads(qkv, hb, ht, inner), self._heads(qkv, hb, ht, 2 * inner),
-                         self._heads(ws[f"e.ctx.{j}"], hb, ht, 0), self._heads(dctx, hb, ht, 0), ws[f"e.st.{j}"],
-                         self._heads(dqkv, hb, ht, 0), self._heads(dqkv, hb, ht, inner),
-                         self._heads(dqkv, hb, ht, 2 * inner), rel_bias=ws["e.rel"], drel=drel_e, rel_off=L - 1,
-                         drop=dr(_enc_site(i, 0)), **akw)
-            dw.append((dqkv, ws[f"e.xn1.{j}"], lw["qkv"].g, 1.0))
-            ops.gemm_nt(dqkv, lw["qkv"].wt, dxe)
-            dw_layers.append(i)
-            if i % grp == 0:      # the group is complete: its launch goes out before the norm backward below rewrites the slot of layer i − 1
-                ops.gemm_tn_grouped(dw, split_k=enc_split if grp > 1 else 0, workspace=self._tn_scratch)
-                dw = []
-            dy_f = self._buf(tmp, "e.dy.ffn" + slot_of(i - 1), (Me, d)) if fused and i > 0 else None
-            ops.rmsnorm_bwd(dxe, ws[f"e.h{i}"], lw["ln1"].p, ws[f"e.rs1.{j}"], deh, deh, lw["ln1"].g,
-                            **self._nxt((dy_f, dr(_enc_site(i - 1, 3))) if fused and i > 0 else None))
+        dw = []
+
+        def flush(i):      # a complete group goes out before layer i's last norm backward rewrites the slot of layer i − 1
             if i % grp == 0:
-                for li in dw_layers:
+                ops.gemm_tn_grouped(list(dw), split_k=bw.enc_split if grp > 1 else 0, workspace=self._tn_scratch)
+                dw.clear()
+
+        for i in reversed(range(Le)):
+            self._enc_layer_bwd(ws, tmp, i, ctx, bw, dr, deh, dxe, drel_e, dw, slot, flush)
+            if i % grp == 0:      # the group that layer i completes: its gradients are final
+                for li in reversed(range(i, min(i + grp, Le))):
                     self._ready(f"enc.{li}.qkv", f"enc.{li}.ln2")
-                dw_layers = []
-        self._embed_bwd(ctx.enc_ids, deh, dr(S_ENC_EMBED))
-        ops.relpos_reduce(drel_e, self._lut(L, L, True), self.enc_rel.g)
-        self._ready("enc.rel", "shared")
-        self.step_count += 1   # next forward draws fresh dropout masks
-        self.ctx = None
+
+    def _enc_layer_bwd(self, ws, tmp, i, ctx, bw, dr, deh, dxe, drel_e, dw, slot, flush):
+        """Backward of _enc_layer_fwd: deh holds the gradient wrt the block's output on entry and wrt its input on exit.
+        The layer's four weight gradients (K = all tokens, small M×N) go into `dw` for ONE grouped launch (with those of the other
+        layers of its group): 108 tiles per layer fill the chip with ~2 K-splits, where four separate launches need 7–28 splits each
+        and pay one fp32 atomic pass over the output per split.  Their operands: the scratch `slot(i)` names; `flush(i)` sends the group."""
+        cfg, ops, lw, rag, p, fused = self.cfg, self.ops, self.enc[i], ctx.rag, bw.p, bw.fused
+        d, inner, L, BN, Me = cfg.d_model, cfg.inner_dim, ctx.L, ctx.B * ctx.N, deh.shape[0]
+        j, sl = i, slot(i)
+        buf = lambda name, cols: self._buf(tmp, name, (Me, cols))                                  # noqa: E731
+        if ctx.ckpt:   # recompute this block's intermediates from its saved input (same seeds → same dropout masks)
+            j = 0
+            self._enc_layer_fwd(ws, i, 0, ws[f"e.h{i}"], None, BN, L, ctx.enc_mask, ws["e.rel"], dr, rag)
+
+        def wgrad(w, dy):
+            x = ws[f"e.{_ENC_DW_X[w]}.{j}"]
+            if p == 0 and w in ("wo", "o"):      # (no dropout: dy IS the residual gradient deh, which the next ops rewrite)
+                ops.gemm_tn(dy, x, lw[w].g)
+            else:
+                dw.append((dy, x, lw[w].g, 1.0))
+
+        # ---- FFN ------------------------------------------------------------------------------
+        nxt = (buf("e.dy" + sl, d), dr(_enc_site(i, 1))) if fused else None
+        self._ffn_bwd(lw, deh, buf("e.dy.ffn" + sl, d) if p > 0 else None, ws[f"e.a1.{j}"], ws[f"e.pre.{j}"] if cfg.gated else None, bw,
+                      dr(_enc_site(i, 2)), dr(_enc_site(i, 3)), buf, ("e.dpre" + sl, "e.dha"), dxe, wgrad, library_gated=True)
+        ops.rmsnorm_bwd(dxe, ws[f"e.h1.{j}"], lw["ln2"].p, ws[f"e.rs2.{j}"], deh, deh, lw["ln2"].g, **self._nxt(nxt))
+        # ---- self-attention ----------------------------------------------------------------------
+        dy = self._branch_grad(deh, buf("e.dy" + sl, d) if p > 0 else None, dr(_enc_site(i, 1)), fused)
+        wgrad("o", dy)
+        dctx = buf("e.dctx", inner)
+        ops.gemm_nt(dy, lw["o"].wt, dctx)
+        qkv, dqkv = ws[f"e.qkv.{j}"], buf("e.dqkv" + sl, 3 * inner)
+        hb, ht, akw = self._enc_attn_layout(rag, BN, L, ctx.enc_mask)
+        ops.attn_bwd(self._heads(qkv, hb, ht, 0), self._heads(qkv, hb, ht, inner), self._heads(qkv, hb, ht, 2 * inner),
+                     self._heads(ws[f"e.ctx.{j}"], hb, ht, 0), self._heads(dctx, hb, ht, 0), ws[f"e.st.{j}"],
+                     self._heads(dqkv, hb, ht, 0), self._heads(dqkv, hb, ht, inner), self._heads(dqkv, hb, ht, 2 * inner),
+                     rel_bias=ws["e.rel"], drel=drel_e, rel_off=L - 1, drop=dr(_enc_site(i, 0)), **akw)
+        wgrad("qkv", dqkv)
+        ops.gemm_nt(dqkv, lw["qkv"].wt, dxe)
+        flush(i)
+        nxt = (buf("e.dy.ffn" + slot(i - 1), d), dr(_enc_site(i - 1, 3))) if fused and i > 0 else None
+        ops.rmsnorm_bwd(dxe, ws[f"e.h{i}"], lw["ln1"].p, ws[f"e.rs1.{j}"], deh, deh, lw["ln1"].g, **self._nxt(nxt))
 
     # ------------------------------------------------------------------------------------------
     # greedy decode  (HF generate: num_beams=1, do_sample=False, use_cache=True), and sampled decode (do_sample=True: temperature,

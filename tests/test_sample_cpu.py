@@ -205,6 +205,21 @@ def test_the_engines_public_calls_issue_the_ops_they_issued_before_the_engine_wa
         assert names == want[call], call
 
 
+@pytest.mark.parametrize("fixture", ["tiny_a", "tiny_eos", "gated_tiny", "legacy_cross_bias"])
+def test_backward_issues_the_ops_it_issued_before_it_was_cut_into_parts(fixture):
+    """tests/golden/engine_bwd_ops.json: the op names of one forward + backward under every switch and state that makes backward branch
+    (tools/op_trace.py's backward variants, the places of the gradient hook's notifications among them), recorded with the tool's own
+    proxy on the commit before Engine.backward came to be a sequence of parts with one feed-forward backward for both stacks"""
+    from tools.op_trace import BWD_FIXTURES, cpu_backward_matrix, read_names
+    want = {key: names for key, names in read_names(os.path.join(GOLDEN, "engine_bwd_ops.json")).items()
+            if key.startswith(fixture + "|") or "+" + fixture in key}
+    got = {key: [r[0] for r in rec["ops"]] for key, rec in cpu_backward_matrix({}, names_only=True, only=fixture).items()}
+    assert fixture in BWD_FIXTURES and sorted(got) == sorted(want) and len(got) == {"tiny_a": 12, "tiny_eos": 12, "gated_tiny": 1}.get(fixture, 2)
+    assert fixture not in ("tiny_a", "tiny_eos") or sum("grad_ready" in names for names in got.values()) == 2
+    for key, names in got.items():
+        assert names == want[key], key
+
+
 def test_the_restatement_follows_the_definition_on_a_hand_made_row():
     x = torch.tensor([0.0, 2.0, 2.0, -float("inf"), 1.0, float("nan")])
     # top_k = 1: the first of the two maxima, whatever the draw

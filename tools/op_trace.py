@@ -10,6 +10,17 @@ untouched, so the engine takes the branches it takes without the proxy and a tra
 
     python tools/op_trace.py [--engine PATH/engine.py] [--out trace.json]          the CPU matrix (fp32 test double)
     python tools/op_trace.py --gpu [--engine …] [--out …]                          the GPU matrix (HipOps, bf16)
+    python tools/op_trace.py [--engine …] --bwd-names FILE                         the names-only golden of the backward variants
+
+The CPU matrix runs every public call under the switches that move the forward side, and one forward + backward under everything that
+makes Engine.backward branch (tiny_a and tiny_eos, dropout 0.1): LAKO_FUSE_DROP=0, LAKO_DEC_DEFER_DW=0, LAKO_DEC_HB_DEFER=0,
+LAKO_ENC_DW_GROUP=1, LAKO_ENC_DW_SPLIT=2, LAKO_DEC_CHAINS=2 with LAKO_DEC_DEFER_DW=0, LAKO_XATTN=0 with LAKO_FUSE_DROP=0,
+set_checkpoint(True), dropout 0 in training mode, a second step without zero_grad, and Engine.grad_hook in overlap and in deferred mode
+(every notification is the pseudo-record ["grad_ready", lo, hi] at its place among the launches); gated_tiny under LAKO_FUSE_DROP=0;
+legacy_cross_bias under LAKO_DEC_CHAINS=2 on mid_a (one chain: three samples) and tiny_eos (two).  The GPU matrix adds the four single
+switches and set_checkpoint(True) on its two training models.  Every record also lists each workspace's allocations (name, shape,
+dtype) in the order the engine first asked for them.  `--bwd-names FILE` writes the op names of the CPU backward variants alone:
+tests/golden/engine_bwd_ops.json.
 
 `--engine` names the file to load as the engine module (default: lako_amd/engine.py), so a saved copy of another commit's engine can be
 traced with everything else equal.  Prints one SHA-256 per (fixture, environment, call); `--out` keeps the full traces for a diff."""
@@ -30,8 +41,8 @@ PASS_THROUGH = ("probe", "det", "xattn_decode_multi_tiles", "mx_scale_cols")    
 
 
 class OpTrace:
-    def __init__(self, inner):
-        self._i, self.records, self.model = inner, [], None
+    def __init__(self, inner, names_only=False):
+        self._i, self.records, self.model, self._names_only = inner, [], None, names_only
 
     def __getattr__(self, n):
         v = getattr(self._i, n)
@@ -39,6 +50,9 @@ class OpTrace:
             return v
 
         def op(*a, **k):
+            if self._names_only:
+                self.records.append([n])
+                return v(*a, **k)
             names = self._buffers()
             self.records.append([n, [self._enc(x, names) for x in a], {key: self._enc(x, names) for key, x in sorted(k.items())}])
             return v(*a, **k)
@@ -120,12 +134,25 @@ def digest(*tensors):
     return h.hexdigest()
 
 
+def allocations(model):
+    """{workspace: [[name, shape, dtype] of every "^" allocation, in the order the engine first asked for them]}"""
+    eng, out = getattr(model, "_engine", None), {}
+
+    def walk(ws, prefix):
+        out[prefix] = [[k, list(t.shape), str(t.dtype)] for k, t in ws.items() if isinstance(k, str) and k.startswith("^") and torch.is_tensor(t)]
+        if isinstance(ws.get("tail"), dict):
+            walk(ws["tail"], prefix + "/tail")
+    for key, ws in (eng._ws_cache.items() if eng is not None else ()):
+        walk(ws, repr(key))
+    return out
+
+
 def record(out, key, ops, fn, results=True):
-    """run fn() under the proxy: out[key] = {ops: […], result: digest of what fn returned}"""
+    """run fn() under the proxy: out[key] = {ops: […], result: digest of what fn returned, allocs: allocations() after the call}"""
     ops.records = []
     got = fn()
     got = got if isinstance(got, (tuple, list)) else (got,)
-    out[key] = dict(ops=ops.records, result=digest(*got) if results else None)
+    out[key] = dict(ops=ops.records, result=digest(*got) if results else None, allocs=allocations(ops.model))
     ops.records = []
 
 
@@ -148,16 +175,60 @@ def candidates(B, C, T, V):
     return cand
 
 
-def calls(out, tag, model, ops, ids, mask, labels, V, multi=True, score=True, results=True):
-    """the public calls of the issue's list on one model"""
-    def fwd_bwd():
-        model.train()
-        model.zero_grad()
+# ---- backward's branches: forward + backward only ------------------------------------------------------------------------------
+BWD_ENVS = {
+    "fuse_drop0": {"LAKO_FUSE_DROP": "0"},
+    "defer_dw0": {"LAKO_DEC_DEFER_DW": "0"},
+    "hb_defer0": {"LAKO_DEC_HB_DEFER": "0"},
+    "enc_dw_group1": {"LAKO_ENC_DW_GROUP": "1"},
+    "enc_dw_split2": {"LAKO_ENC_DW_SPLIT": "2"},
+    "chains2+defer_dw0": {"LAKO_DEC_CHAINS": "2", "LAKO_DEC_DEFER_DW": "0"},
+    "xattn0+fuse_drop0": {"LAKO_XATTN": "0", "LAKO_FUSE_DROP": "0"},
+}
+# what is not a switch of the environment: {name: keyword arguments of backward_case}
+BWD_STATES = {
+    "checkpoint": dict(checkpoint=True),
+    "dropout0": dict(dropout=0.0),                  # training mode without dropout: the p == 0 branches
+    "accumulate": dict(steps=2),                    # a second forward + backward without zero_grad: the gradients add
+    "hook_overlap": dict(hook=True),                # Engine.grad_hook in overlap mode (grad_ranges_early): no grouping across layers
+    "hook_deferred": dict(hook=False),
+}
+BWD_FIXTURES = ("tiny_a", "tiny_eos", "gated_tiny", "legacy_cross_bias")
+GPU_BWD = ("fuse_drop0", "defer_dw0", "hb_defer0", "enc_dw_group1", "checkpoint")
+
+
+def fwd_bwd(model, ids, mask, labels, steps=1):
+    model.train()
+    model.zero_grad()
+    for _ in range(steps):
         res = model(input_ids=ids, attention_mask=mask, labels=labels)
         res[0].backward()
-        model.eval()
-        return res[0].detach(), res.logits.detach(), model._engine.G
-    record(out, f"{tag}|forward_backward", ops, fwd_bwd, results)
+    model.eval()
+    return res[0].detach(), res.logits.detach(), model._engine.G
+
+
+def backward_case(out, key, model, ops, ids, mask, labels, results=True, checkpoint=False, steps=1, hook=None):
+    """record one forward + backward; `hook` (True: overlap mode, False: deferred) sets Engine.grad_hook to a function that appends
+    the pseudo-record ["grad_ready", lo, hi], so that the place of every notification among the launches is part of the trace"""
+    model.set_checkpoint(checkpoint)
+    if hook is not None:
+        eng = model._get_engine()
+        eng.grad_hook, eng.grad_ranges_early = (lambda lo, hi: ops.records.append(["grad_ready", lo, hi])), hook
+    record(out, key, ops, lambda: fwd_bwd(model, ids, mask, labels, steps), results)
+
+
+def backward_variants(out, tag, build, names=None, **kw):
+    """every variant of BWD_ENVS and BWD_STATES (or those in `names`) on a fresh model from build(dropout) → (model, ops, batch)"""
+    for name in names or (*BWD_ENVS, *BWD_STATES):
+        state = dict(BWD_STATES.get(name, {}))
+        with environment(BWD_ENVS.get(name, {})):
+            model, ops, batch = build(state.pop("dropout", 0.1))
+            backward_case(out, f"{tag}|{name}|forward_backward", model, ops, *batch, **state, **kw)
+
+
+def calls(out, tag, model, ops, ids, mask, labels, V, multi=True, score=True, results=True):
+    """the public calls of the issue's list on one model"""
+    record(out, f"{tag}|forward_backward", ops, lambda: fwd_bwd(model, ids, mask, labels), results)
     record(out, f"{tag}|generate_greedy", ops, lambda: model.generate(ids, mask, 6))
     record(out, f"{tag}|generate_sampled", ops, lambda: model.generate(ids, mask, 6, do_sample=True, top_k=3, seed=7, return_scores=True,
                                                                         num_return_sequences=3 if multi else 1))
@@ -166,7 +237,8 @@ def calls(out, tag, model, ops, ids, mask, labels, V, multi=True, score=True, re
         record(out, f"{tag}|score", ops, lambda: model.score(ids, mask, cand, candidate_chunk=2))
 
 
-def cpu_matrix():
+def cpu_build(name, gated=False, legacy=False, dropout=0.1, names_only=False):
+    """→ (model on the traced fp32 test double, the proxy, [input_ids, attention_mask, labels], vocabulary size)"""
     import dataclasses
 
     from lako_amd import FiDT5
@@ -178,20 +250,39 @@ def cpu_matrix():
     class GatedOps(GatedRefOps, RefOpsSample):
         pass
 
-    def build(name, gated=False, legacy=False):
-        torch.manual_seed(0)
-        z, dims, w = (load_gated if gated else load_case)(name)
-        cfg = gated_cfg(dims, 0.1) if gated else cfg_of(dims, 0.1)
-        if legacy:
-            cfg = dataclasses.replace(cfg, legacy_cross_bias=True)
-        ops = OpTrace(GatedOps() if gated else RefOpsSample())
-        model = FiDT5(cfg, dtype=torch.float32, _ops=ops)
-        if not legacy:      # (the fixture has no cross-attention table: the seeded initial weights)
-            model.load_t5(w)
-        ops.model = model
-        model.eval()
-        return model, ops, [torch.from_numpy(z[k]) for k in ("input_ids", "attention_mask", "labels")], dims.vocab_size
+    torch.manual_seed(0)
+    z, dims, w = (load_gated if gated else load_case)(name)
+    cfg = gated_cfg(dims, dropout) if gated else cfg_of(dims, dropout)
+    if legacy:
+        cfg = dataclasses.replace(cfg, legacy_cross_bias=True)
+    ops = OpTrace(GatedOps() if gated else RefOpsSample(), names_only)
+    model = FiDT5(cfg, dtype=torch.float32, _ops=ops)
+    if not legacy:      # (the fixture has no cross-attention table: the seeded initial weights)
+        model.load_t5(w)
+    ops.model = model
+    model.eval()
+    return model, ops, [torch.from_numpy(z[k]) for k in ("input_ids", "attention_mask", "labels")], dims.vocab_size
 
+
+def cpu_backward_matrix(out, names_only=False, only=None):
+    """backward's branches on the double (the module docstring lists them); `only`: one of BWD_FIXTURES"""
+    def of(name, **kw):
+        return lambda dropout: cpu_build(name, dropout=dropout, names_only=names_only, **kw)[:3]
+    for name in ("tiny_a", "tiny_eos"):
+        if only in (None, name):
+            backward_variants(out, name, of(name))
+    if only in (None, "gated_tiny"):
+        backward_variants(out, "gated_tiny", of("gated_tiny", gated=True), names=["fuse_drop0"])
+    if only in (None, "legacy_cross_bias"):
+        with environment({"LAKO_DEC_CHAINS": "2"}):      # the cross-attention table's gradient; tiny_eos has the four samples two chains need
+            for name in ("mid_a", "tiny_eos"):
+                model, ops, batch = of(name, legacy=True)(0.1)
+                backward_case(out, f"{name}+legacy_cross_bias|chains2|forward_backward", model, ops, *batch)
+    return out
+
+
+def cpu_matrix():
+    build = cpu_build
     out = {}
     for name in ("tiny_a", "tiny_eos"):
         for env_name, env in ENVS.items():
@@ -207,7 +298,7 @@ def cpu_matrix():
     model.overwrite_forward_crossattention()
     model.reset_score_storage()
     record(out, "tiny_a|default|generate_capture_scores", ops, lambda: (model.generate(batch[0], batch[1], 6), model._score_storage))
-    return out
+    return cpu_backward_matrix(out)
 
 
 # ---- the GPU matrix ------------------------------------------------------------------------------------------------------------
@@ -215,6 +306,8 @@ def gpu_matrix():
     """bf16 on HipOps, on the smallest cases the kernels' gates accept (the builders of tests/test_sample_gpu.py and
     tests/test_score_gpu.py): what the double does not have — the one-pass decode kernels, gemm_nt_four, the fp8 norm + quantise path —
     and the graph regime: eager warm-up, capture, replay, each call's tokens and scores digested."""
+    import dataclasses
+
     from lako_amd import FiDConfig, FiDT5
     from lako_amd.ops import HipOps
     from oracle import fid_t5_oracle as O
@@ -239,22 +332,43 @@ def gpu_matrix():
                     record(out, f"{tag}|generate_sampled_K{K}", ops, lambda: model.generate(
                         ids, mask, ML, do_sample=True, top_k=3, num_return_sequences=K, seed=7, return_scores=True))
     # forward + backward + score where the encoder-state cross-attention runs (tests/test_score_gpu.py's model)
-    torch.manual_seed(17)
     cfg = FiDConfig(vocab_size=64, d_model=128, d_kv=64, d_ff=256, num_layers=2, num_decoder_layers=2, num_heads=2, dropout_rate=0.1)
-    for fp8 in (False, True):
+
+    def score_model(dropout=0.1, fp8=False):
         torch.manual_seed(17)
-        model = FiDT5(cfg, dtype=torch.bfloat16, fp8=fp8).cuda().eval()
-        ops = traced(model)
-        ids, mask, labels = (t.cuda() for t in O.synthetic_batch(2, 3, 24, 4, cfg.vocab_size, seed=23))
-        calls(out, f"score_model{'+fp8' if fp8 else ''}|default", model, ops, ids, mask, labels, cfg.vocab_size, results=False)
+        model = FiDT5(dataclasses.replace(cfg, dropout_rate=dropout), dtype=torch.bfloat16, fp8=fp8).cuda().eval()
+        return model, traced(model), [t.cuda() for t in O.synthetic_batch(2, 3, 24, 4, cfg.vocab_size, seed=23)]
+
+    for fp8 in (False, True):
+        model, ops, batch = score_model(fp8=fp8)
+        calls(out, f"score_model{'+fp8' if fp8 else ''}|default", model, ops, *batch, cfg.vocab_size, results=False)
+    backward_variants(out, "score_model", score_model, names=GPU_BWD, results=False)
     z, dims, w = load_gated("gated_mid")
-    model = FiDT5(gated_cfg(dims, 0.1), dtype=torch.bfloat16)
-    model.load_t5(w)
-    model = model.cuda().eval()
-    ops = traced(model)
-    ids, mask, labels = (torch.from_numpy(z[k]).cuda() for k in ("input_ids", "attention_mask", "labels"))
-    calls(out, "gated_mid|default", model, ops, ids, mask, labels, dims.vocab_size, results=False)
+
+    def gated_mid(dropout=0.1):
+        model = FiDT5(gated_cfg(dims, dropout), dtype=torch.bfloat16)
+        model.load_t5(w)
+        model = model.cuda().eval()
+        return model, traced(model), [torch.from_numpy(z[k]).cuda() for k in ("input_ids", "attention_mask", "labels")]
+
+    model, ops, batch = gated_mid()
+    calls(out, "gated_mid|default", model, ops, *batch, dims.vocab_size, results=False)
+    backward_variants(out, "gated_mid", gated_mid, names=GPU_BWD, results=False)
     return out
+
+
+def write_names(path, traces):
+    """{trace key: op names} as a table of the names and one line of indices into it per trace"""
+    names = sorted({n for t in traces.values() for n in t})
+    rows = [f"{json.dumps(k)}: {json.dumps([names.index(n) for n in t], separators=(',', ':'))}" for k, t in sorted(traces.items())]
+    with open(path, "w") as fh:
+        fh.write('{"names": ' + json.dumps(names) + ',\n"traces": {\n' + ",\n".join(rows) + "\n}}\n")
+
+
+def read_names(path):
+    with open(path) as fh:
+        doc = json.load(fh)
+    return {k: [doc["names"][i] for i in t] for k, t in doc["traces"].items()}
 
 
 def main():
@@ -262,8 +376,12 @@ def main():
     ap.add_argument("--engine", help="file to load as the engine module (default: lako_amd/engine.py)")
     ap.add_argument("--out", help="write the full traces here (JSON)")
     ap.add_argument("--gpu", action="store_true", help="the GPU matrix (HipOps, bf16) instead of the CPU one")
+    ap.add_argument("--bwd-names", help="write {trace key: op names} of the CPU backward variants here and stop (tests/golden/engine_bwd_ops.json)")
     a = ap.parse_args()
     use_engine(a.engine)
+    if a.bwd_names:
+        write_names(a.bwd_names, {k: [r[0] for r in v["ops"]] for k, v in cpu_backward_matrix({}, names_only=True).items()})
+        return
     out = gpu_matrix() if a.gpu else cpu_matrix()
     for key, rec in out.items():
         body = json.dumps(rec, sort_keys=True).encode()
